@@ -10,6 +10,10 @@ all back + sync. `value` is the whole-job aggregate GB/s of payload moved
 
 Launch (driver contract):
     python bench.py --gpus N --steps K --warmup W
+A plain run sets up, warms up, times the K steps and prints the result line.
+`--full` additionally measures the sequential commit-to-commit put/get rates
+and the single-block p50/p99 latency (null in a plain run's `config`);
+`--dump-outputs DIR` writes what the last timed step read back.
 For N>1 the driver uses torch.distributed.run with one rank per GPU; rank r
 runs a client on GPU r, rank 0 additionally hosts the in-process server
 sharded over all N GPUs (weak scaling: per-GPU work is fixed).
@@ -29,12 +33,22 @@ import torch
 def parse_args():
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
-    p.add_argument("--steps", type=int, default=10)
+    p.add_argument("--steps", type=int, default=10,
+                   help="timed steps. Every step stores fresh keys; when all "
+                        "of them fit in the pool nothing is freed inside the "
+                        "timed region, otherwise each worker deletes its "
+                        "oldest step's keys while the next copies run (see "
+                        "--pool-cap-gb)")
     p.add_argument("--warmup", type=int, default=3)
     p.add_argument("--block-kb", type=int, default=128)
     p.add_argument("--blocks", type=int, default=2048,
                    help="blocks per rank per step (2048 x 128KB = 256 MB)")
     p.add_argument("--pool-gb", type=int, default=8, help="pool GB per shard")
+    p.add_argument("--pool-cap-gb", type=int, default=0,
+                   help="upper bound for the pool GB per shard (GPU mode; "
+                        "default: the GPU's free memory less room for the "
+                        "client buffers). A run whose keys would not fit "
+                        "below it keeps only the newest steps in the store")
     p.add_argument("--port", type=int, default=0)
     p.add_argument("--server-addr", default="127.0.0.1",
                    help="connect to an external server instead of hosting one "
@@ -65,7 +79,63 @@ def parse_args():
                         "request packing on the GIL (~1.4 TB/s ceiling); "
                         "separate processes reach the server's real "
                         "capacity. 0 = legacy threaded mode (--conns).")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run the secondary "
+                        "measurements (sequential commit-to-commit put/get "
+                        "rates, single-block p50/p99 latency); a plain run "
+                        "reports them as null")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step read back from the "
+                        "store as DIR/<name>.npy (float32; a fixed seeded "
+                        "sample when the payload exceeds the size budget)")
     return p.parse_args()
+
+
+# --dump-outputs budget for the whole job (all ranks and workers together):
+# well under 64 MB, so a dump stays cheap to write, keep and compare.
+DUMP_BUDGET_BYTES = 32 << 20
+
+
+def _dump_sample_index(blocks, elems_per_block, budget_elems, seed):
+    """Element indices of a buffer of `blocks` pages to dump, or None for all
+    of it. Stratified so every page is represented: the same seeded set of
+    within-page positions (always including element 0, which carries the
+    per-step salt) is taken from each page. Depends only on its arguments,
+    so two runs with the same command line sample the same elements."""
+    import numpy as np
+
+    if blocks * elems_per_block <= budget_elems:
+        return None
+    rng = np.random.default_rng(seed)
+    per_block = budget_elems // blocks
+    if per_block == 0:  # more pages than budget: a seeded subset of pages
+        pages = np.sort(rng.choice(blocks, size=max(budget_elems, 1),
+                                   replace=False))
+        per_block = 1
+    else:
+        pages = np.arange(blocks)
+    within = rng.choice(elems_per_block, size=per_block, replace=False)
+    if 0 not in within:
+        within[0] = 0
+    within.sort()
+    return (pages[:, None].astype(np.int64) * elems_per_block
+            + within[None, :].astype(np.int64)).ravel()
+
+
+def dump_read_buffer(dump_dir, name, buf, blocks, elems_per_block, n_parts,
+                     seed):
+    """Write `buf` (the destination of the last timed read) to
+    dump_dir/name.npy as float32, sampled to this part's share of the job's
+    dump budget."""
+    import numpy as np
+
+    budget_elems = DUMP_BUDGET_BYTES // 4 // max(n_parts, 1)
+    idx = _dump_sample_index(blocks, elems_per_block, budget_elems, seed)
+    if idx is not None:
+        buf = buf[torch.from_numpy(idx).to(buf.device)]
+    os.makedirs(dump_dir, exist_ok=True)
+    np.save(os.path.join(dump_dir, name + ".npy"),
+            buf.float().cpu().numpy())
 
 
 def _proc_worker(cfg, barrier, q):
@@ -124,6 +194,18 @@ def _proc_worker(cfg, barrier, q):
                 rc.read_pages(dsts[d], wk1, offs[:1], elems_per_block)
                 rc.sync()
         blobs = [pk(keys(s)) for s in range(K)]
+        # Bounded store (the run's keys do not all fit in the pool): only
+        # the newest `ring` steps stay resident. The keys of step s+3-ring
+        # are deleted over a third connection right after W(s+2) and R(s+1)
+        # have been queued, so the delete overlaps their copies and its
+        # blocks are free again before W(s+3) allocates. The step was read
+        # back long before (ring >= 4 > pipeline depth).
+        ring = cfg["ring"] if 0 < cfg["ring"] < K else 0
+        dc, del_keys = None, {}
+        if ring:
+            dc = ifs.InfinityConnection(ccfg)
+            dc.connect()
+            del_keys = {j: keys(j) for j in range(K - ring)}
         torch.cuda.synchronize()
 
         barrier.wait(timeout=600)  # ready: all workers warmed up
@@ -143,6 +225,8 @@ def _proc_worker(cfg, barrier, q):
             tk_next = (rc.read_pages_async(dsts[(s + 1) % 2], blobs[s + 1],
                                            offs, elems_per_block)
                        if s + 1 < K else None)
+            if ring and ring <= s + 3 < K:
+                dc.delete_keys(del_keys.pop(s + 3 - ring))
             rc.wait_read(tk)
             wc.sync()
             tk = tk_next
@@ -157,8 +241,15 @@ def _proc_worker(cfg, barrier, q):
                                            atol=float(sb.abs().max()) * 0.07)
             else:
                 ok = ok and torch.equal(sb.cpu(), db.cpu())
+        if cfg["dump_dir"]:
+            dump_read_buffer(cfg["dump_dir"],
+                             f"get_r{cfg['rank']}w{cfg['wid']}",
+                             dsts[(K - 1) % 2], blocks, elems_per_block,
+                             cfg["n_parts"], seed=cfg["wid"])
         wc.close()
         rc.close()
+        if dc is not None:
+            dc.close()
         q.put((cfg["wid"], ok, ""))
     except Exception as e:  # pragma: no cover - surfaced via parent assert
         try:
@@ -169,14 +260,12 @@ def _proc_worker(cfg, barrier, q):
 
 
 def run_procs_mode(args, rank, world, local_rank, dist, port, block_bytes,
-                   elems_per_block):
+                   elems_per_block, ring=0):
     """Local-path timed loop with worker PROCESSES instead of threads (each
     conn pair owns a GIL). The parent aligns ranks, brackets the timed
     region with barriers, then runs the latency phase and the sequential
     per-direction phase itself."""
     import multiprocessing
-
-    import numpy as np
 
     import infinistore_amd as ifs
 
@@ -198,7 +287,8 @@ def run_procs_mode(args, rank, world, local_rank, dist, port, block_bytes,
         cfg = dict(rank=rank, wid=w, local_rank=local_rank, port=port,
                    blocks=worker_blocks[w], elems_per_block=elems_per_block,
                    steps=args.steps, warmup=args.warmup, quant=args.quant,
-                   run_id=run_id)
+                   run_id=run_id, dump_dir=args.dump_outputs,
+                   n_parts=P * world, ring=ring)
         pr = ctx.Process(target=_proc_worker, args=(cfg, barrier, q))
         pr.start()
         workers.append(pr)
@@ -238,7 +328,77 @@ def run_procs_mode(args, rank, world, local_rank, dist, port, block_bytes,
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t[0])
 
-    # ---- parent-side phases (latency + sequential per-direction) ----
+    seq_steps, seq_put, seq_get, lat_put, lat_get = 0, 0.0, 0.0, [], []
+    if args.full:
+        seq_steps, seq_put, seq_get, lat_put, lat_get = _procs_full_phases(
+            args, rank, local_rank, dist, port, elems_per_block, run_id)
+
+    def pct(v, qq):
+        if not v:
+            return 0.0 if args.full else None
+        return round(statistics.quantiles(v, n=100)[qq - 1]
+                     if len(v) >= 10 else max(v), 1)
+
+    bytes_per_step_rank = args.blocks * block_bytes
+    gbps = 2.0 * bytes_per_step_rank * args.steps * world / 1e9 / elapsed
+    put_gbps = (bytes_per_step_rank * seq_steps * world / 1e9 / seq_put
+                if seq_put > 0 else None)
+    get_gbps = (bytes_per_step_rank * seq_steps * world / 1e9 / seq_get
+                if seq_get > 0 else None)
+    if rank == 0:
+        result = {
+            "metric": "put_get_GBps",
+            "value": round(gbps, 3),
+            "unit": "GB/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": round(elapsed / args.steps * 1000, 3),
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "bf16+fp8kv" if args.quant else "bf16",
+            "data": "synthetic",
+            "config": {
+                "model": "kvcache-store",
+                "block_kb": args.block_kb,
+                "blocks_per_rank_per_step": args.blocks,
+                "global_batch": args.blocks * world,
+                "seq_len": 0,
+                "parallelism": f"shard{world}",
+                "path": "local_gpu_ipc",
+                "client_procs": P,
+                # steps kept resident in the store (null: all of them)
+                "resident_steps": ring if 0 < ring < args.steps else None,
+                # the fields below are measured only with --full
+                "put_GBps": round(put_gbps, 3) if put_gbps else None,
+                "get_GBps": round(get_gbps, 3) if get_gbps else None,
+                "p50_put_us": pct(lat_put, 50),
+                "p99_put_us": pct(lat_put, 99),
+                "p50_get_us": pct(lat_get, 50),
+                "p99_get_us": pct(lat_get, 99),
+            },
+        }
+        print(json.dumps(result))
+    if dist:
+        dist.barrier()
+    if rank == 0 and not (args.server_addr != "127.0.0.1"):
+        print("server stats:", ifs.get_server_stats(), file=sys.stderr)
+        ifs.unregister_server()
+    if dist:
+        dist.destroy_process_group()
+
+
+def _procs_full_phases(args, rank, local_rank, dist, port, elems_per_block,
+                       run_id):
+    """--full only: the parent-side secondary measurements of the process
+    mode, run after the timed region (sequential per-direction rates, then
+    single-block latency). Returns (seq_steps, seq_put_s, seq_get_s,
+    lat_put_us, lat_get_us)."""
+    import numpy as np
+
+    import infinistore_amd as ifs
+
     ccfg = ifs.ClientConfig(host_addr="127.0.0.1", service_port=port,
                             connection_type=ifs.TYPE_LOCAL_GPU)
     conn = ifs.InfinityConnection(ccfg)
@@ -305,56 +465,7 @@ def run_procs_mode(args, rank, world, local_rank, dist, port, block_bytes,
     if dist:
         dist.barrier()
 
-    def pct(v, qq):
-        if not v:
-            return 0.0
-        return statistics.quantiles(v, n=100)[qq - 1] if len(v) >= 10 else max(v)
-
-    bytes_per_step_rank = args.blocks * block_bytes
-    gbps = 2.0 * bytes_per_step_rank * args.steps * world / 1e9 / elapsed
-    put_gbps = (bytes_per_step_rank * seq_steps * world / 1e9 / seq_put
-                if seq_put > 0 else None)
-    get_gbps = (bytes_per_step_rank * seq_steps * world / 1e9 / seq_get
-                if seq_get > 0 else None)
-    if rank == 0:
-        result = {
-            "metric": "put_get_GBps",
-            "value": round(gbps, 3),
-            "unit": "GB/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1000, 3),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "bf16+fp8kv" if args.quant else "bf16",
-            "data": "synthetic",
-            "config": {
-                "model": "kvcache-store",
-                "block_kb": args.block_kb,
-                "blocks_per_rank_per_step": args.blocks,
-                "global_batch": args.blocks * world,
-                "seq_len": 0,
-                "parallelism": f"shard{world}",
-                "path": "local_gpu_ipc",
-                "client_procs": P,
-                "put_GBps": round(put_gbps, 3) if put_gbps else None,
-                "get_GBps": round(get_gbps, 3) if get_gbps else None,
-                "p50_put_us": round(pct(lat_put, 50), 1),
-                "p99_put_us": round(pct(lat_put, 99), 1),
-                "p50_get_us": round(pct(lat_get, 50), 1),
-                "p99_get_us": round(pct(lat_get, 99), 1),
-            },
-        }
-        print(json.dumps(result))
-    if dist:
-        dist.barrier()
-    if rank == 0 and not (args.server_addr != "127.0.0.1"):
-        print("server stats:", ifs.get_server_stats(), file=sys.stderr)
-        ifs.unregister_server()
-    if dist:
-        dist.destroy_process_group()
+    return seq_steps, seq_put, seq_get, lat_put, lat_get
 
 
 def main():
@@ -379,6 +490,7 @@ def main():
     port = args.port or (23000 + (os.getpid() % 1000) if world == 1 else 23999)
 
     external = args.server_addr != "127.0.0.1"
+    ring = 0  # steps kept resident when the keys outgrow the pool (0: all)
     # Rank 0 hosts the server, sharded over all visible GPUs.
     if rank == 0 and not external:
         n_shards = min(n_gpus, torch.cuda.device_count()) if have_gpu else 1
@@ -389,6 +501,29 @@ def main():
         need_bytes = (args.steps + args.warmup) * args.blocks * args.block_kb * 1024
         need_gb = (need_bytes * ranks_per_shard * 5) // (4 << 30) + 1  # +25% slack
         pool_gb = max(args.pool_gb, int(need_gb))
+        if have_gpu:
+            # The pool cannot outgrow the GPU. Leave room for the clients on
+            # the same device (4 source + 2 destination buffers per rank, 2
+            # more with --full, and a HIP context per process), and when the
+            # run's keys do not fit under the cap keep only the newest `ring`
+            # steps resident, filling the pool to 90% (pages are all one
+            # allocation unit, so there is no fragmentation to allow for).
+            step_bytes = args.blocks * args.block_kb * 1024 * ranks_per_shard
+            free_b = min(torch.cuda.mem_get_info(d)[0] for d in range(n_shards))
+            cap_gb = int((free_b - 8 * step_bytes) >> 30) - 12
+            if args.pool_cap_gb:
+                cap_gb = min(cap_gb, args.pool_cap_gb)
+            if pool_gb > cap_gb:
+                pool_gb = max(cap_gb, 1)
+                ring = (int((pool_gb << 30) * 0.9) // step_bytes
+                        - max(args.warmup, 1) - 1)
+                if ring >= args.steps:
+                    ring = 0  # everything fits after all
+                elif ring < 4:
+                    print(json.dumps({"error": "pool of %d GB is too small "
+                                      "for a step of %d MB" % (
+                                          pool_gb, step_bytes >> 20)}))
+                    sys.exit(1)
         scfg = ifs.ServerConfig(
             service_port=port,
             manage_port=port + 1,
@@ -400,7 +535,9 @@ def main():
         )
         ifs.register_server(scfg)
     if dist:
-        dist.barrier()
+        obj = [ring]
+        dist.broadcast_object_list(obj, src=0)
+        ring = obj[0]
 
     block_bytes = args.block_kb * 1024
     elems_per_block = block_bytes // 2  # bf16
@@ -411,7 +548,12 @@ def main():
     if (args.procs > 0 and use_local_path_early and not (args.cross and world > 1)
             and not args.no_pipeline and not os.environ.get("IFS_BENCH_DEBUG")):
         return run_procs_mode(args, rank, world, local_rank, dist, port,
-                              block_bytes, elems_per_block)
+                              block_bytes, elems_per_block, ring)
+    if ring:
+        print(json.dumps({"error": "--steps %d does not fit in the pool; only "
+                          "the process mode (--procs > 0) can bound the "
+                          "store" % args.steps}))
+        sys.exit(1)
 
     if have_gpu:
         torch.cuda.set_device(local_rank)
@@ -688,6 +830,10 @@ def main():
     verify("timed loop", args.steps - 1)
     if args.steps > 1:
         verify("timed loop", args.steps - 2)
+    if args.dump_outputs:
+        dump_read_buffer(args.dump_outputs, f"get_r{rank}",
+                         dsts[(args.steps - 1) % 2], args.blocks,
+                         elems_per_block, world, seed=0)
     if debug:
         per = {k: round(v / args.steps * 1e6, 1) for k, v in debug_t.items()}
         print(f"rank {rank} per-step us: {per}", file=sys.stderr)
@@ -706,7 +852,7 @@ def main():
     # time of async writes as put_GBps — 2-3x the sustainable rate). Measure
     # put and get separately: each put timed to commit-ACK (sync), each get
     # to completion.
-    seq_steps = min(args.steps, 4) if pipeline else 0
+    seq_steps = min(args.steps, 4) if (pipeline and args.full) else 0
     seq_put = seq_get = 0.0
     for s in range(seq_steps):
         ks = [f"seq-{k}" for k in put_keys[s]]
@@ -724,10 +870,11 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         seq_put, seq_get = t.tolist()
 
-    # ---- latency phase (single-block round trips) ----
+    # ---- latency phase (single-block round trips; --full only) ----
     lat_put, lat_get = [], []
-    lkeys = [f"lat-r{rank}-{run_id}-{i}" for i in range(args.latency_ops)]
-    for i in range(args.latency_ops):
+    latency_ops = args.latency_ops if args.full else 0
+    lkeys = [f"lat-r{rank}-{run_id}-{i}" for i in range(latency_ops)]
+    for i in range(latency_ops):
         t1 = time.perf_counter()
         if use_local_path:
             conn.local_gpu_write_cache(src, [(lkeys[i], 0)], elems_per_block)
@@ -746,8 +893,9 @@ def main():
 
     def pct(v, q):
         if not v:
-            return 0.0
-        return statistics.quantiles(v, n=100)[q - 1] if len(v) >= 10 else max(v)
+            return 0.0 if args.full else None
+        return round(statistics.quantiles(v, n=100)[q - 1]
+                     if len(v) >= 10 else max(v), 1)
 
     bytes_per_step_rank = args.blocks * block_bytes
     total_gb = 2.0 * bytes_per_step_rank * args.steps * world / 1e9  # put+get
@@ -787,13 +935,15 @@ def main():
                 "seq_len": 0,
                 "parallelism": f"shard{world}",
                 "path": "local_gpu_ipc" if use_local_path else ("fabric_remote" if external else "tcp_fabric_cpu"),
-                # sequential commit-to-commit rates (sustained, unpipelined)
+                # sequential commit-to-commit rates (sustained, unpipelined;
+                # in the pipelined mode measured only with --full, like the
+                # latency percentiles)
                 "put_GBps": round(put_gbps, 3) if put_gbps else None,
                 "get_GBps": round(get_gbps, 3) if get_gbps else None,
-                "p50_put_us": round(pct(lat_put, 50), 1),
-                "p99_put_us": round(pct(lat_put, 99), 1),
-                "p50_get_us": round(pct(lat_get, 50), 1),
-                "p99_get_us": round(pct(lat_get, 99), 1),
+                "p50_put_us": pct(lat_put, 50),
+                "p99_put_us": pct(lat_put, 99),
+                "p50_get_us": pct(lat_get, 50),
+                "p99_get_us": pct(lat_get, 99),
             },
         }
         print(json.dumps(result))

@@ -4,7 +4,7 @@
 #   ./scripts/validate.sh quick    # suite only
 # GPU-side equivalents (run on an MI355X box):
 #   python -m pytest tests -q -m gpu
-#   python bench.py --steps 30 --warmup 3
+#   python bench.py --steps 30 --warmup 3 --full
 #   python scripts/soak.py --seconds 60 --threads 6 --quant-frac 0.4
 set -e
 cd "$(dirname "$0")/.."

@@ -277,7 +277,7 @@ def test_native_extension_is_loaded():
 def test_bench_smoke():
     env = dict(os.environ)
     r = subprocess.run(
-        [sys.executable, "bench.py", "--steps", "3", "--warmup", "1",
+        [sys.executable, "bench.py", "--full", "--steps", "3", "--warmup", "1",
          "--blocks", "256", "--latency-ops", "30", "--pool-gb", "2"],
         cwd=REPO, env=env, capture_output=True, text=True, timeout=420,
     )
@@ -286,6 +286,79 @@ def test_bench_smoke():
     out = json.loads(line)
     assert out["metric"] == "put_get_GBps" and out["value"] > 0
     assert out["config"]["path"] == "local_gpu_ipc"
+    # --full: the secondary measurements are present
+    assert out["config"]["put_GBps"] > 0 and out["config"]["get_GBps"] > 0
+    assert out["config"]["p50_put_us"] > 0 and out["config"]["p99_get_us"] > 0
+
+
+def test_bench_plain_dump_outputs(tmp_path):
+    """A plain run times exactly --steps steps, skips the secondary
+    measurements and, with --dump-outputs, writes what the last timed step
+    read back: one float32 file per client worker, every page sampled at the
+    same positions, element 0 of each page carrying that step's salt."""
+    import numpy as np
+
+    steps, blocks, procs, page_elems = 3, 256, 4, 128 * 1024 // 2
+    r = subprocess.run(
+        [sys.executable, "bench.py", "--gpus", "1", "--steps", str(steps),
+         "--warmup", "1", "--blocks", str(blocks), "--pool-gb", "2",
+         "--dump-outputs", str(tmp_path)],
+        cwd=REPO, env=dict(os.environ), capture_output=True, text=True,
+        timeout=420,
+    )
+    assert r.returncode == 0, r.stdout + r.stderr
+    line = [l for l in r.stdout.strip().splitlines() if l.startswith("{")][-1]
+    out = json.loads(line)
+    assert out["metric"] == "put_get_GBps" and out["value"] > 0
+    assert out["steps"] == steps and out["ms_per_step"] > 0
+    # value and ms_per_step describe the same timed region (ms_per_step is
+    # rounded to 1 us, i.e. to within 5% for any step of 10 us or longer)
+    gb_per_step = 2 * blocks * 128 * 1024 / 1e9
+    assert out["value"] == pytest.approx(
+        gb_per_step / (out["ms_per_step"] / 1e3), rel=5e-2)
+    for k in ("put_GBps", "get_GBps", "p50_put_us", "p99_get_us"):
+        assert out["config"][k] is None
+    files = sorted(p.name for p in tmp_path.iterdir())
+    assert files == [f"get_r0w{w}.npy" for w in range(procs)]
+    total = 0
+    for f in files:
+        a = np.load(tmp_path / f)
+        assert a.dtype == np.float32 and np.isfinite(a).all()
+        total += a.nbytes
+        pages = a.reshape(blocks // procs, -1)
+        assert pages.shape[1] <= page_elems
+        # the last timed step (index steps-1) writes salt steps
+        assert (pages[:, 0] == float(steps)).all()
+        assert pages[:, 1:].std() > 0.5  # randn payload, not zeros
+    assert total <= 64 << 20
+
+
+def test_bench_bounded_store(tmp_path):
+    """More timed steps than the pool can hold: the run keeps only the
+    newest steps resident (deleting the oldest step's keys as it goes) and
+    still verifies and dumps the last step. 11 steps of 1024 x 128 KB
+    against a 1 GB pool = 8192 blocks, of which 90% minus the warmup keys
+    leave room for 5 steps."""
+    import numpy as np
+
+    steps, blocks, procs = 11, 1024, 4
+    r = subprocess.run(
+        [sys.executable, "bench.py", "--gpus", "1", "--steps", str(steps),
+         "--warmup", "1", "--blocks", str(blocks), "--pool-gb", "1",
+         "--pool-cap-gb", "1", "--dump-outputs", str(tmp_path)],
+        cwd=REPO, env=dict(os.environ), capture_output=True, text=True,
+        timeout=420,
+    )
+    assert r.returncode == 0, r.stdout + r.stderr
+    line = [l for l in r.stdout.strip().splitlines() if l.startswith("{")][-1]
+    out = json.loads(line)
+    assert out["steps"] == steps and out["value"] > 0
+    assert out["config"]["resident_steps"] == 5
+    for w in range(procs):
+        a = np.load(tmp_path / f"get_r0w{w}.npy")
+        pages = a.reshape(blocks // procs, -1)
+        # last step index 10 -> salt (10 % 4) + 1
+        assert (pages[:, 0] == 3.0).all() and pages[:, 1:].std() > 0.5
 
 
 def test_cross_gpu_read(gpu_server):
