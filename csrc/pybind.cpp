@@ -571,6 +571,53 @@ PYBIND11_MODULE(_native, m) {
                               flow.parked());
     });
 
+    // KvIndex harness: run (op, keys) steps against one small index through
+    // the server's batched sweep; entries carry no block (null shard/ptr).
+    // insert -> won flags, find -> present flags, extract/size/clear -> count.
+    m.def("_dbg_kvindex_ops",
+          [](const std::vector<std::pair<std::string, std::vector<std::string>>>& steps) {
+        using L = KvIndex::Lock;
+        KvIndex idx(/*ttl_seconds=*/0, /*stripe_slots=*/4);
+        idx.reserve(64);  // small: rehash + tombstone reuse run
+        py::list out;
+        for (auto& [op, keys] : steps) {
+            const size_t n = keys.size();
+            std::vector<uint64_t> h(n);
+            for (size_t i = 0; i < n; i++) h[i] = KvIndex::hash_of(keys[i]);
+            std::vector<bool> flags(n);
+            std::vector<Ref<BlockEntry>> dropped;  // displaced / extracted refs
+            if (op == "insert") {
+                SlabBatch slab(n);
+                idx.for_each_batched<L::kExclusive>(
+                    n, h.data(), KvIndex::rotated_start(h.data(), n), [&](KvMap& m, size_t i) {
+                        Ref<BlockEntry> e(slab.make());
+                        flags[i] = idx.insert_locked(m, keys[i], h[i], e, true, &dropped);
+                        if (!flags[i]) dropped.push_back(std::move(e));  // loser
+                        return true;
+                    });
+                out.append(flags);
+            } else if (op == "find") {
+                idx.for_each_batched<L::kShared>(n, h.data(), 0, [&](KvMap& m, size_t i) {
+                    flags[i] = idx.find_live(m, keys[i], h[i]) != nullptr;
+                    return true;
+                });
+                out.append(flags);
+            } else if (op == "extract") {
+                idx.for_each_batched<L::kExclusive>(n, h.data(), 0, [&](KvMap& m, size_t i) {
+                    Ref<BlockEntry> ref;
+                    if (m.extract(keys[i], &ref)) dropped.push_back(std::move(ref));
+                    return true;
+                });
+                out.append(dropped.size());
+            } else if (op == "size" || op == "clear") {
+                out.append(op == "size" ? idx.size() : idx.clear());
+            } else {
+                throw std::runtime_error("unknown op " + op);
+            }
+        }
+        return out;
+    });
+
     // Mempool (host-backed) for allocator unit tests.
     py::class_<MemoryPool>(m, "_TestPool")
         .def(py::init([](size_t size, size_t block_size) {

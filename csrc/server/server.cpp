@@ -12,128 +12,18 @@
 
 namespace ifs {
 
-// ---------------------------------------------------------------------------
-// BlockEntry slab allocator (entries churn by the thousands per request)
-// ---------------------------------------------------------------------------
 namespace {
-struct EntrySlab {
-    std::mutex mu;
-    std::vector<void*> free_list;
-    std::vector<std::unique_ptr<char[]>> chunks;
-    static constexpr size_t kPerChunk = 4096;
 
-    void* take_locked(size_t n) {
-        if (free_list.empty()) {
-            chunks.emplace_back(new char[n * kPerChunk]);
-            char* base = chunks.back().get();
-            free_list.reserve(kPerChunk);
-            for (size_t i = 0; i < kPerChunk; i++) free_list.push_back(base + i * n);
-        }
-        void* p = free_list.back();
-        free_list.pop_back();
-        return p;
-    }
-
-    // Thread-local magazines: entry alloc/free happens on every handler,
-    // completion and delete path — one global mutex per op (especially
-    // give(), which delete churn hit ~6M times per 64-client run) serialized
-    // the whole server. Each thread caches up to kMagMax entries and
-    // exchanges them with the global list kMagBatch at a time.
-    static constexpr size_t kMagBatch = 256;
-    static constexpr size_t kMagMax = 512;
-    struct Magazine {
-        std::vector<void*> items;
-        ~Magazine();  // flush to the global list (pollers exit per conn)
-    };
-    static Magazine& mag() {
-        thread_local Magazine m;
-        return m;
-    }
-
-    void* take(size_t n) {
-        auto& m = mag();
-        if (m.items.empty()) {
-            std::lock_guard<std::mutex> lk(mu);
-            m.items.reserve(kMagMax);
-            for (size_t i = 0; i < kMagBatch; i++) m.items.push_back(take_locked(n));
-        }
-        void* p = m.items.back();
-        m.items.pop_back();
-        return p;
-    }
-    // Bulk take for a write batch: drain the magazine, top up from the
-    // global list under ONE lock.
-    void take_bulk(size_t n, size_t count, std::vector<void*>* out) {
-        auto& m = mag();
-        while (count && !m.items.empty()) {
-            out->push_back(m.items.back());
-            m.items.pop_back();
-            count--;
-        }
-        if (count) {
-            std::lock_guard<std::mutex> lk(mu);
-            for (size_t i = 0; i < count; i++) out->push_back(take_locked(n));
-        }
-    }
-    void give(void* p) {
-        auto& m = mag();
-        m.items.push_back(p);
-        if (m.items.size() >= kMagMax) {
-            std::lock_guard<std::mutex> lk(mu);
-            for (size_t i = 0; i < kMagBatch; i++) {
-                free_list.push_back(m.items.back());
-                m.items.pop_back();
-            }
-        }
-    }
-    void give_bulk(std::vector<void*>& items, size_t from) {
-        auto& m = mag();
-        for (size_t i = from; i < items.size(); i++) m.items.push_back(items[i]);
-        if (m.items.size() >= kMagMax) {
-            std::lock_guard<std::mutex> lk(mu);
-            while (m.items.size() > kMagBatch) {
-                free_list.push_back(m.items.back());
-                m.items.pop_back();
-            }
-        }
-    }
-};
-EntrySlab& entry_slab() {
-    // Intentionally leaked: entries may still be freed during interpreter
-    // teardown after static destructors would have run.
-    static EntrySlab* s = new EntrySlab();
-    return *s;
+// IFS_SERVER_DEBUG: per-request phase timing on stderr (docs/perf_notes.md).
+// Read once, at the first request.
+bool debug_on() {
+    static const bool on = getenv("IFS_SERVER_DEBUG") != nullptr;
+    return on;
 }
-
-EntrySlab::Magazine::~Magazine() {
-    if (items.empty()) return;
-    auto& s = entry_slab();  // leaked singleton: safe at thread exit
-    std::lock_guard<std::mutex> lk(s.mu);
-    for (void* p : items) s.free_list.push_back(p);
+using Clock = std::chrono::steady_clock;
+double us(Clock::time_point a, Clock::time_point b) {
+    return std::chrono::duration<double, std::micro>(b - a).count();
 }
-}  // namespace
-
-void* BlockEntry::operator new(size_t n) { return entry_slab().take(n); }
-void BlockEntry::operator delete(void* p) { entry_slab().give(p); }
-
-namespace {
-// One lock for a whole burst of entry allocations (hot write path).
-struct SlabBatch {
-    std::vector<void*> slots;
-    size_t next = 0;
-    explicit SlabBatch(size_t count) {
-        slots.reserve(count);
-        entry_slab().take_bulk(sizeof(BlockEntry), count, &slots);
-    }
-    ~SlabBatch() {
-        if (next >= slots.size()) return;
-        entry_slab().give_bulk(slots, next);
-    }
-    BlockEntry* make() { return new (slots[next++]) BlockEntry(); }
-};
-}  // namespace
-
-namespace {
 
 struct WriteReq {
     uv_write_t req;
@@ -223,7 +113,7 @@ void send_buf(Server::Conn* c, std::vector<uint8_t> data) {
 // ---------------------------------------------------------------------------
 // Server lifecycle
 // ---------------------------------------------------------------------------
-Server::Server(const ServerOptions& opt) : opt_(opt) {
+Server::Server(const ServerOptions& opt) : opt_(opt), index_(opt.ttl_seconds) {
     set_log_level(opt.log_level.c_str());
     if (opt_.devices.empty()) {
         for (int i = 0; i < std::max(1, opt_.cpu_shards); i++) {
@@ -335,7 +225,7 @@ bool Server::start() {
     size_t kv_initial = std::max<size_t>(1u << 20, pool_blocks + pool_blocks / 2);
     kv_initial = std::min<size_t>(kv_initial, 1u << 24);
     if (const char* env = getenv("IFS_KV_INITIAL")) kv_initial = strtoull(env, nullptr, 10);
-    for (auto& st : kv_) st.map.reserve(kv_initial / kStripes);
+    index_.reserve(kv_initial);
     running_.store(true);
     stop_requested_.store(false);
     // Fast-op workers (ring write/read handlers): enough to keep every HIP
@@ -354,32 +244,15 @@ bool Server::start() {
     for (auto& w : workers_) w->start();
     if (opt_.ttl_seconds > 0) {
         ttl_thread_ = std::thread([this] {
-            // Sweep every ttl/4 (>=1 s): one bounded pass over each stripe,
-            // erasing expired idle entries. Lookups already treat expired
+            // Sweep every ttl/4 (>=1 s): one pass over the index erasing
+            // expired idle entries. Lookups already treat expired
             // keys as absent; this just returns their memory early.
             auto period = std::chrono::seconds(std::max(1, opt_.ttl_seconds / 4));
             std::unique_lock<std::mutex> lk(ttl_mu_);
             while (!ttl_cv_.wait_for(lk, period,
                                      [this] { return stop_requested_.load(); })) {
                 lk.unlock();
-                size_t swept = 0;
-                for (auto& st : kv_) {
-                    std::vector<Ref<BlockEntry>> dead;  // dropped after unlock
-                    {
-                        std::lock_guard<std::shared_mutex> ex(st.mu);
-                        std::vector<std::string> victims;
-                        st.map.for_each([&](std::string_view key, Ref<BlockEntry>& val) {
-                            if (expired(val.get()) && val->ref_count() == 1)
-                                victims.emplace_back(key);
-                        });
-                        dead.reserve(victims.size());
-                        for (auto& k : victims) {
-                            Ref<BlockEntry> ref;
-                            if (st.map.extract(k, &ref)) dead.emplace_back(std::move(ref));
-                        }
-                        swept += victims.size();
-                    }
-                }
+                size_t swept = index_.sweep_expired();
                 if (swept) DEBUG("ttl sweep: %zu expired entries erased", swept);
                 lk.lock();
             }
@@ -790,96 +663,6 @@ Shard* Server::shard_least_used() {
     return best;
 }
 
-uint32_t Server::now_sec() {
-    struct timespec ts;
-    clock_gettime(CLOCK_MONOTONIC, &ts);
-    return static_cast<uint32_t>(ts.tv_sec);
-}
-
-void Server::erase_entries(const std::vector<Ref<BlockEntry>>& entries) {
-    // Rare path (allocation failure / failed copy): remove entries from the
-    // index by identity. O(map) scan, but keys are not kept around on the
-    // hot path. One stripe at a time.
-    for (auto& st : kv_) {
-        std::vector<Ref<BlockEntry>> dead;  // dropped after unlock
-        {
-            std::lock_guard<std::shared_mutex> lk(st.mu);
-            std::vector<std::string> victims;
-            st.map.for_each([&](std::string_view key, Ref<BlockEntry>& val) {
-                for (auto& e : entries)
-                    if (val.get() == e.get()) victims.emplace_back(key);
-            });
-            dead.reserve(victims.size());
-            for (auto& k : victims) {
-                Ref<BlockEntry> ref;
-                if (st.map.extract(k, &ref)) dead.emplace_back(std::move(ref));
-            }
-        }
-    }
-}
-
-size_t Server::evict_lru(Shard* shard, size_t bytes) {
-    // Sampled clock-hand eviction: scan bounded slot windows from a
-    // persistent per-stripe cursor, evict the least-recently-accessed half
-    // of each sample — O(evicted) amortized instead of a full index scan
-    // per eviction event (which capped sustained full-pool churn).
-    // Candidates: committed, idle (only the map holds a ref), on this shard.
-    // Key views stay valid across erase (the arena is append-only).
-    // Stripes are visited round-robin (shared cursor) holding one stripe
-    // lock at a time.
-    size_t freed = 0;
-    // NOTE on fresh writes: the sample sort below already evicts oldest
-    // first, so recently written keys survive unless a sample is entirely
-    // fresh (possible at ~100% occupancy — the pool is then genuinely too
-    // small for the working set and evicting fresh data is the honest LRU
-    // outcome). An explicit freshness-exemption pass was tried and reverted:
-    // at full occupancy it degenerated to an O(map) rescan per allocation
-    // (13x soak throughput collapse).
-    for (size_t visited = 0; freed < bytes && visited < kStripes; visited++) {
-        auto& st = kv_[evict_stripe_rr_.fetch_add(1) % kStripes];
-        std::vector<Ref<BlockEntry>> dead;  // block frees run after unlock
-        std::lock_guard<std::shared_mutex> lk(st.mu);
-        size_t scanned = 0;
-        const size_t scan_cap = st.map.capacity();  // one revolution max
-        std::vector<std::pair<uint64_t, std::string_view>> sample;
-        sample.reserve(128);
-        while (freed < bytes && scanned < scan_cap) {
-            size_t window = 4096;
-            st.map.scan_from(&st.evict_hand, window,
-                             [&](std::string_view key, Ref<BlockEntry>& val) {
-                                 BlockEntry* e = val.get();
-                                 uint64_t la = e->last_access.load(std::memory_order_relaxed);
-                                 if (e->shard == shard && e->committed && e->ref_count() == 1)
-                                     sample.push_back(
-                                         {expired(e) ? 0  // expired: evict first
-                                                     : la,
-                                          key});
-                                 return sample.size() < 128;
-                             });
-            scanned += window;
-            // In a sparse table one window yields few candidates; evicting
-            // from a 1-2 entry "sample" degrades LRU to "next key after the
-            // cursor". Accumulate across windows until the sample is big
-            // enough to rank (or the stripe is fully scanned).
-            if (sample.size() < 128 && scanned < scan_cap) continue;
-            if (sample.empty()) break;
-            std::sort(sample.begin(), sample.end(),
-                      [](const auto& a, const auto& b) { return a.first < b.first; });
-            size_t take = std::max<size_t>(1, sample.size() / 2);
-            for (size_t i = 0; i < take && freed < bytes; i++) {
-                Ref<BlockEntry> ref;
-                if (!st.map.extract(sample[i].second, &ref)) continue;
-                freed += ref->size;
-                dead.emplace_back(std::move(ref));
-                n_evicted_.fetch_add(1);
-            }
-            sample.clear();
-        }
-    }
-    if (freed) DEBUG("auto-evicted %zu bytes from shard dev=%d", freed, shard->device());
-    return freed;
-}
-
 void Server::maybe_extend(Shard* s) {
     if (!s->need_extend()) return;
     int expect = 0;
@@ -954,8 +737,8 @@ struct IpcPinGuard {
 }  // namespace
 
 void Server::op_local_write(Conn* c, const LocalView& msg, const ReqCtx& ctx) {
-    static const bool pdbg = getenv("IFS_SERVER_DEBUG") != nullptr;
-    auto p0 = std::chrono::steady_clock::now();
+    const bool dbg = debug_on();
+    auto p0 = Clock::now();
     if (!gpu::available()) return reply_local(c, ctx, SYSTEM_ERROR);
     if (msg.ipc_len != gpu::kIpcHandleSize || msg.block_size <= 0)
         return reply_local(c, ctx, INVALID_REQ);
@@ -967,7 +750,6 @@ void Server::op_local_write(Conn* c, const LocalView& msg, const ReqCtx& ctx) {
     Shard* shard = shard_for_device(msg.device);
     size_t page = static_cast<size_t>(msg.block_size);
     size_t nb = msg.blocks.size();
-    constexpr size_t kPf = 16;
     // fp8 ingest compression (extension): bf16 pages stored at half size
     // with one scale per page; requires a 16-byte-divisible page.
     const bool quant = (msg.flags & kLocalFlagQuantFp8) != 0;
@@ -978,47 +760,24 @@ void Server::op_local_write(Conn* c, const LocalView& msg, const ReqCtx& ctx) {
     // The authoritative first-write-wins decision happens at the insert pass
     // (phase D); a key that appears between A and D just wastes one block
     // copy whose memory is released after the kernel completes.
+    // An empty request sweeps nothing and replies like an all-duplicates one.
     std::vector<uint64_t> hashes(nb);
-    for (size_t i = 0; i < nb; i++) hashes[i] = KvMap::hash_of(msg.blocks[i].first);
+    for (size_t i = 0; i < nb; i++) hashes[i] = KvIndex::hash_of(msg.blocks[i].first);
     std::vector<uint32_t> fresh;
     fresh.reserve(nb);
-    // Bucket keys by stripe once; each stripe's lookups run under that
-    // stripe's SHARED lock (~nb/16 keys per hold), so concurrent requests
-    // on other stripes never wait.
-    std::array<std::vector<uint32_t>, kStripes> by_stripe;
-    for (size_t i = 0; i < nb; i++)
-        by_stripe[stripe_of(hashes[i])].push_back(static_cast<uint32_t>(i));
-    // Random start: concurrent requests sweeping stripes in the same
-    // ascending order convoy on every lock in turn.
-    size_t sweep0 = static_cast<size_t>(hashes[0] >> 32) % kStripes;
-    double lw_us = 0, ul_us = 0;  // lock-wait vs under-lock (pdbg)
-    for (size_t sk = 0; sk < kStripes; sk++) {
-        size_t si = (sweep0 + sk) % kStripes;
-        auto& list = by_stripe[si];
-        if (list.empty()) continue;
-        auto tl0 = pdbg ? std::chrono::steady_clock::now()
-                        : std::chrono::steady_clock::time_point{};
-        std::shared_lock<std::shared_mutex> lk(kv_[si].mu);
-        auto tl1 = pdbg ? std::chrono::steady_clock::now()
-                        : std::chrono::steady_clock::time_point{};
-        auto& m = kv_[si].map;
-        size_t ln = list.size();
-        for (size_t i = 0; i < std::min(kPf, ln); i++) m.prefetch(hashes[list[i]]);
-        for (size_t i = 0; i < ln; i++) {
-            if (i + kPf < ln) m.prefetch(hashes[list[i + kPf]]);
-            uint32_t gi = list[i];
-            Ref<BlockEntry>* v = m.find_hashed(msg.blocks[gi].first, hashes[gi]);
-            if (!v || expired(v->get())) fresh.push_back(gi);
-        }
-        if (pdbg) {
-            auto tl2 = std::chrono::steady_clock::now();
-            lw_us += std::chrono::duration<double, std::micro>(tl1 - tl0).count();
-            ul_us += std::chrono::duration<double, std::micro>(tl2 - tl1).count();
-        }
-    }
-    if (pdbg && nb > 64)
-        fprintf(stderr, "[pdbg2] dedup lockwait=%.0f underlock=%.0f\n", lw_us, ul_us);
-    auto p1 = std::chrono::steady_clock::now();
+    KvIndex::SweepTimes ta, td;  // lock-wait vs under-lock (dbg)
+    index_.for_each_batched<KvIndex::Lock::kShared>(
+        nb, hashes.data(), KvIndex::rotated_start(hashes.data(), nb),
+        [&](KvMap& m, size_t i) {
+            if (!index_.find_live(m, msg.blocks[i].first, hashes[i]))
+                fresh.push_back(static_cast<uint32_t>(i));
+            return true;
+        },
+        dbg ? &ta : nullptr);
+    if (dbg && nb > 64)
+        fprintf(stderr, "[pdbg2] dedup lockwait=%.0f underlock=%.0f\n", ta.lock_wait_us,
+                ta.under_lock_us);
+    auto p1 = Clock::now();
 
     n_writes_.fetch_add(1);
     size_t n_fresh = fresh.size();
@@ -1043,15 +802,15 @@ void Server::op_local_write(Conn* c, const LocalView& msg, const ReqCtx& ctx) {
     // freed blocks to a racing allocation; keep evicting until the
     // allocation lands or eviction runs dry.
     for (int attempt = 0; !alloc_ok && opt_.auto_evict && attempt < 4; attempt++) {
-        if (evict_lru(shard, page * n_fresh * 2) == 0) break;
+        if (index_.evict_lru(shard, page * n_fresh * 2) == 0) break;
         alloc_ok = try_alloc();
     }
     if (!alloc_ok) return reply_local(c, ctx, OUT_OF_MEMORY);
-    auto p2 = std::chrono::steady_clock::now();
+    auto p2 = Clock::now();
 
     // Phase C — create entries, build the copy job and LAUNCH it; the index
     // insert pass (D) then runs while the kernel is in flight.
-    uint64_t t = tick();
+    uint64_t t = index_.tick();
     SlabBatch slab_batch(n_fresh);
     auto entries = std::make_shared<std::vector<Ref<BlockEntry>>>();
     entries->reserve(n_fresh);
@@ -1073,7 +832,7 @@ void Server::op_local_write(Conn* c, const LocalView& msg, const ReqCtx& ctx) {
         e->shard = shard;
         e->committed = false;
         e->fp8 = quant;
-        e->born_sec = now_sec();
+        e->born_sec = KvIndex::now_sec();
         e->last_access.store(t, std::memory_order_relaxed);
         entries->emplace_back(e);
         job.src.push_back(
@@ -1084,8 +843,7 @@ void Server::op_local_write(Conn* c, const LocalView& msg, const ReqCtx& ctx) {
 
     c->remain.fetch_add(1);
     c->ref();
-    static const bool sdbg = getenv("IFS_SERVER_DEBUG") != nullptr;
-    auto t_start = std::chrono::steady_clock::now();
+    auto t_start = Clock::now();
     // won[i] is written in phase D after the kernel is submitted. The commit
     // must see phase D's result, so it runs on whichever side finishes LAST:
     // both the copy-done callback and the end of phase D bump `arrivals`,
@@ -1106,30 +864,25 @@ void Server::op_local_write(Conn* c, const LocalView& msg, const ReqCtx& ctx) {
                     (*entries)[i]->committed = true;
                 }
         } else {
-            // Copy failed: drop the keys. Always from the owner loop —
-            // erase_entries takes the kv lock exclusively, and compact()
-            // waits on completion-thread futures WHILE holding that
-            // lock, so taking it on a completion thread could deadlock.
+            // Copy failed: drop the keys. Always from the owner loop, never
+            // a completion thread (kv_index.h invariants): erase_entries is
+            // an O(index) scan under exclusive stripe locks.
             c->ref();
             c->owner->post([this, c, entries, won] {
                 std::vector<Ref<BlockEntry>> winners;
                 for (size_t i = 0; i < entries->size(); i++)
                     if ((*won)[i]) winners.push_back((*entries)[i]);
-                erase_entries(winners);
+                index_.erase_entries(winners);
                 c->unref();
             });
         }
         if (sync_resp) reply_local(c, ctx, ok ? FINISH : INTERNAL_ERROR);
         finish_task(c, /*on_owner=*/!ctx.shm);
     };
-    job.done = [this, c, entries, fin, ctx, copy_ok, arrivals, t_start](bool ok) {
-        if (sdbg && entries->size() > 64) {
-            auto us = std::chrono::duration<double, std::micro>(
-                          std::chrono::steady_clock::now() - t_start)
-                          .count();
+    job.done = [this, c, entries, fin, ctx, copy_ok, arrivals, t_start, dbg](bool ok) {
+        if (dbg && entries->size() > 64)
             fprintf(stderr, "[sdbg] write n=%zu submit->complete=%.0fus\n", entries->size(),
-                    us);
-        }
+                    us(t_start, Clock::now()));
         copy_ok->store(ok, std::memory_order_release);
         if (ctx.shm) {
             // Never block the completion thread: if phase D has not ended,
@@ -1148,68 +901,34 @@ void Server::op_local_write(Conn* c, const LocalView& msg, const ReqCtx& ctx) {
     // response sent on completion instead. Ring async writes are unacked.
     if (!sync_resp && !ctx.shm) send_status(c, TASK_ACCEPTED);
     bool submitted = shard->submit_copy(std::move(job));
-    auto p2b = std::chrono::steady_clock::now();
+    auto p2b = Clock::now();
 
     // Phase D — insert pass, overlapped with the in-flight kernel. Losers
     // (a racing writer inserted the key first) keep their block alive until
     // the copy completes, then release it; they are never committed.
     {
-        std::array<std::vector<uint32_t>, kStripes> ins_by_stripe;  // pos in fresh
-        for (uint32_t p = 0; p < n_fresh; p++)
-            ins_by_stripe[stripe_of(hashes[fresh[p]])].push_back(p);
-        size_t ins0 = static_cast<size_t>(hashes[fresh[0]] >> 32) % kStripes;
-        double ilw_us = 0, iul_us = 0;
-        for (size_t sk = 0; sk < kStripes; sk++) {
-            size_t si = (ins0 + sk) % kStripes;
-            auto& list = ins_by_stripe[si];
-            if (list.empty()) continue;
-            auto tl0 = pdbg ? std::chrono::steady_clock::now()
-                            : std::chrono::steady_clock::time_point{};
-            std::lock_guard<std::shared_mutex> lk(kv_[si].mu);
-            auto tl1 = pdbg ? std::chrono::steady_clock::now()
-                            : std::chrono::steady_clock::time_point{};
-            struct UlAcc {  // accumulate under-lock time at scope exit
-                bool on;
-                std::chrono::steady_clock::time_point t1;
-                double *lw, *ul;
-                std::chrono::steady_clock::time_point t0;
-                ~UlAcc() {
-                    if (!on) return;
-                    auto t2 = std::chrono::steady_clock::now();
-                    *lw += std::chrono::duration<double, std::micro>(t1 - t0).count();
-                    *ul += std::chrono::duration<double, std::micro>(t2 - t1).count();
-                }
-            } acc{pdbg, tl1, &ilw_us, &iul_us, tl0};
-            auto& m = kv_[si].map;
-            size_t ln = list.size();
-            for (size_t i = 0; i < std::min(kPf, ln); i++) m.prefetch(hashes[fresh[list[i]]]);
-            for (size_t i = 0; i < ln; i++) {
-                if (i + kPf < ln) m.prefetch(hashes[fresh[list[i + kPf]]]);
-                uint32_t p = list[i];
-                bool inserted = false;
-                Ref<BlockEntry>* slot2 = m.emplace_hashed(msg.blocks[fresh[p]].first,
-                                                          hashes[fresh[p]], (*entries)[p],
-                                                          &inserted);
-                if (!inserted && slot2 && expired(slot2->get())) {
-                    *slot2 = (*entries)[p];  // expired loser: replace in place
-                    inserted = true;
-                }
-                (*won)[p] = inserted ? 1 : 0;
-            }
-        }
-        if (pdbg && n_fresh > 64)
-            fprintf(stderr, "[pdbg2] insert lockwait=%.0f underlock=%.0f\n", ilw_us, iul_us);
+        std::vector<uint64_t> fresh_hashes(n_fresh);
+        for (size_t p = 0; p < n_fresh; p++) fresh_hashes[p] = hashes[fresh[p]];
+        std::vector<Ref<BlockEntry>> displaced;  // expired entries; dropped after the sweep
+        index_.for_each_batched<KvIndex::Lock::kExclusive>(
+            n_fresh, fresh_hashes.data(), KvIndex::rotated_start(fresh_hashes.data(), n_fresh),
+            [&](KvMap& m, size_t p) {
+                (*won)[p] = index_.insert_locked(m, msg.blocks[fresh[p]].first, fresh_hashes[p],
+                                                 (*entries)[p], /*replace_expired=*/true,
+                                                 &displaced);
+                return true;
+            },
+            dbg ? &td : nullptr);
+        if (dbg && n_fresh > 64)
+            fprintf(stderr, "[pdbg2] insert lockwait=%.0f underlock=%.0f\n", td.lock_wait_us,
+                    td.under_lock_us);
     }
     // Phase D done: second arriver commits (the copy may already be done).
     if (submitted && arrivals->fetch_add(1, std::memory_order_acq_rel) == 1) fin();
-    auto p3 = std::chrono::steady_clock::now();
-    if (pdbg && n_fresh > 64) {
-        auto us = [](auto a, auto b) {
-            return std::chrono::duration<double, std::micro>(b - a).count();
-        };
+    auto p3 = Clock::now();
+    if (dbg && n_fresh > 64)
         fprintf(stderr, "[pdbg] dedup=%.0f alloc=%.0f submit=%.0f insert=%.0f\n", us(p0, p1),
                 us(p1, p2), us(p2, p2b), us(p2b, p3));
-    }
     if (!submitted) {
         // The job never launched (e.g. a transform on a CPU shard): the done
         // callback will not fire, so answer sync-response writers here.
@@ -1228,7 +947,7 @@ void Server::op_local_read(Conn* c, const LocalView& msg, const ReqCtx& ctx) {
     uint8_t* client_ptr = static_cast<uint8_t*>(base) + msg.base_offset;
     size_t page = static_cast<size_t>(msg.block_size);
 
-    auto tr0 = std::chrono::steady_clock::now();
+    auto tr0 = Clock::now();
     // Group blocks by the shard whose GPU EXECUTES the copy. For same-GPU
     // hits that is trivially the owner. For cross-shard hits the choice is
     // deliberate: default OWNER-side (push) — the owner's
@@ -1259,51 +978,38 @@ void Server::op_local_read(Conn* c, const LocalView& msg, const ReqCtx& ctx) {
     std::map<Shard*, Shard::CopyJob> qjobs;
     auto held = std::make_shared<std::vector<Ref<BlockEntry>>>();
     held->reserve(msg.blocks.size());
-    uint64_t read_tick = tick();
-    {
-        size_t nb2 = msg.blocks.size();
-        std::vector<uint64_t> hashes(nb2);
-        for (size_t i = 0; i < nb2; i++) hashes[i] = KvMap::hash_of(msg.blocks[i].first);
-        constexpr size_t kPf = 16;
-        std::array<std::vector<uint32_t>, kStripes> by_stripe;
-        for (size_t i = 0; i < nb2; i++)
-            by_stripe[stripe_of(hashes[i])].push_back(static_cast<uint32_t>(i));
-        for (size_t si = 0; si < kStripes; si++) {
-            auto& list = by_stripe[si];
-            if (list.empty()) continue;
-            std::shared_lock<std::shared_mutex> lk(kv_[si].mu);
-            auto& m = kv_[si].map;
-            size_t ln = list.size();
-            for (size_t i = 0; i < std::min(kPf, ln); i++) m.prefetch(hashes[list[i]]);
-            for (size_t i = 0; i < ln; i++) {
-                if (i + kPf < ln) m.prefetch(hashes[list[i + kPf]]);
-                auto& b = msg.blocks[list[i]];
-                Ref<BlockEntry>* v = m.find_hashed(b.first, hashes[list[i]]);
-                if (!v || !(*v)->committed || expired(v->get())) {
-                    return reply_local(c, ctx, KEY_NOT_FOUND);
-                }
-                BlockEntry* e = v->get();
-                e->last_access.store(read_tick, std::memory_order_relaxed);
-                if (e->fp8) {
-                    if (e->size * 2 != page) return reply_local(c, ctx, INVALID_REQ);
-                    auto& qj = qjobs[exec_shard(e->shard)];
-                    qj.bytes_per_block = page;
-                    qj.xform = Shard::CopyJob::Xform::kDequantFp8Bf16;
-                    qj.scales_in.push_back(e->scale);
-                    qj.src.push_back(reinterpret_cast<uint64_t>(e->ptr));
-                    qj.dst.push_back(reinterpret_cast<uint64_t>(client_ptr + b.second));
-                } else {
-                    auto& job = jobs[exec_shard(e->shard)];
-                    job.bytes_per_block = page;
-                    job.src.push_back(reinterpret_cast<uint64_t>(e->ptr));
-                    job.dst.push_back(reinterpret_cast<uint64_t>(client_ptr + b.second));
-                }
-                held->push_back(*v);
+    uint64_t read_tick = index_.tick();
+    std::vector<uint64_t> hashes(msg.blocks.size());
+    for (size_t i = 0; i < hashes.size(); i++) hashes[i] = KvIndex::hash_of(msg.blocks[i].first);
+    int err = 0;  // first failing key ends the sweep
+    index_.for_each_batched<KvIndex::Lock::kShared>(
+        hashes.size(), hashes.data(), 0, [&](KvMap& m, size_t i) {
+            auto& b = msg.blocks[i];
+            Ref<BlockEntry>* v = index_.find_live(m, b.first, hashes[i]);
+            if (!v || !(*v)->committed) {
+                err = KEY_NOT_FOUND;
+                return false;
             }
-        }
-    }
-    static const bool rdbg2 = getenv("IFS_SERVER_DEBUG") != nullptr;
-    auto tcol = std::chrono::steady_clock::now();
+            BlockEntry* e = v->get();
+            e->last_access.store(read_tick, std::memory_order_relaxed);
+            if (e->fp8 && e->size * 2 != page) {
+                err = INVALID_REQ;
+                return false;
+            }
+            auto& job = (e->fp8 ? qjobs : jobs)[exec_shard(e->shard)];
+            job.bytes_per_block = page;
+            if (e->fp8) {
+                job.xform = Shard::CopyJob::Xform::kDequantFp8Bf16;
+                job.scales_in.push_back(e->scale);
+            }
+            job.src.push_back(reinterpret_cast<uint64_t>(e->ptr));
+            job.dst.push_back(reinterpret_cast<uint64_t>(client_ptr + b.second));
+            held->push_back(*v);
+            return true;
+        });
+    if (err) return reply_local(c, ctx, err);
+    const bool dbg = debug_on();
+    auto tcol = Clock::now();
     n_reads_.fetch_add(1);
     bytes_out_.fetch_add(msg.blocks.size() * page);
     bool sync_resp = (msg.flags & kLocalFlagSyncResponse) != 0;
@@ -1317,15 +1023,11 @@ void Server::op_local_read(Conn* c, const LocalView& msg, const ReqCtx& ctx) {
     auto all_ok = std::make_shared<std::atomic<bool>>(true);
     auto submit_one = [&](Shard* shard, Shard::CopyJob& job) -> bool {
         Shard::CopyJob j = std::move(job);
-        static const bool sdbg2 = getenv("IFS_SERVER_DEBUG") != nullptr;
-        auto t_start2 = std::chrono::steady_clock::now();
-        j.done = [this, c, held, pending, all_ok, sync_resp, ctx, t_start2](bool ok) {
-            if (sdbg2 && held->size() > 64) {
-                auto us = std::chrono::duration<double, std::micro>(
-                              std::chrono::steady_clock::now() - t_start2)
-                              .count();
-                fprintf(stderr, "[sdbg] read n=%zu submit->complete=%.0fus\n", held->size(), us);
-            }
+        auto t_start2 = Clock::now();
+        j.done = [this, c, held, pending, all_ok, sync_resp, ctx, t_start2, dbg](bool ok) {
+            if (dbg && held->size() > 64)
+                fprintf(stderr, "[sdbg] read n=%zu submit->complete=%.0fus\n", held->size(),
+                        us(t_start2, Clock::now()));
             if (!ok) all_ok->store(false);
             if (pending->fetch_sub(1) == 1) {
                 if (ctx.shm) {
@@ -1356,14 +1058,9 @@ void Server::op_local_read(Conn* c, const LocalView& msg, const ReqCtx& ctx) {
         if (!submit_one(shard, job)) return;
     for (auto& [shard, job] : qjobs)
         if (!submit_one(shard, job)) return;
-    if (rdbg2 && msg.blocks.size() > 256) {
-        auto us = [](auto a, auto b) {
-            return std::chrono::duration<double, std::micro>(b - a).count();
-        };
-        auto tsub = std::chrono::steady_clock::now();
+    if (dbg && msg.blocks.size() > 256)
         fprintf(stderr, "[rdbg] read n=%zu collect=%.0f submit=%.0f\n", msg.blocks.size(),
-                us(tr0, tcol), us(tcol, tsub));
-    }
+                us(tr0, tcol), us(tcol, Clock::now()));
     if (!sync_resp && !ctx.shm) send_status(c, TASK_ACCEPTED);
 }
 
@@ -1548,8 +1245,7 @@ void Server::shm_poll_main(ShmPeer* p) {
         ReqCtx ctx{h.seq, true};
         auto t0 = std::chrono::steady_clock::now();
         char op = static_cast<char>(h.op);
-        static const bool rdbg = getenv("IFS_SERVER_DEBUG") != nullptr;
-        if (rdbg && h.body_len > 4096)
+        if (debug_on() && h.body_len > 4096)
             fprintf(stderr, "[rdbg] op=%c pickup_wait=%uus\n", op,
                     shmring::mono_us() - h.t_push_us);
         if (h.body_len + sizeof(h) > len) {
@@ -1657,24 +1353,15 @@ std::vector<RemoteBlockWire> Server::allocate_blocks(Conn* c,
     std::vector<std::tuple<std::string, uint64_t, uint64_t>> created;  // key, hash, ptr
     auto rollback = [&] {
         for (auto& [k, h, p] : created) {
-            {
-                auto& st = kv_[stripe_of(h)];
-                std::lock_guard<std::shared_mutex> lk(st.mu);
-                st.map.erase(k);
-            }
+            index_.erase(k, h);
             c->pending_rdma.erase(p);  // drop the ref so the block frees now
         }
     };
     for (auto& key : keys) {
-        uint64_t h = KvMap::hash_of(key);
-        auto& st = kv_[stripe_of(h)];
-        {
-            std::shared_lock<std::shared_mutex> sl(st.mu);
-            Ref<BlockEntry>* v0 = st.map.find_hashed(key, h);
-            if (v0 != nullptr && !expired(v0->get())) {
-                blocks.push_back({0, 0, 0});  // FAKE block: dup key, client skips
-                continue;
-            }
+        uint64_t h = KvIndex::hash_of(key);
+        if (index_.lookup(key, h)) {
+            blocks.push_back({0, 0, 0});  // FAKE block: dup key, client skips
+            continue;
         }
         void* ptr = nullptr;
         int pool_idx = -1;
@@ -1686,7 +1373,7 @@ std::vector<RemoteBlockWire> Server::allocate_blocks(Conn* c,
         };
         bool ok = try_alloc();
         for (int attempt = 0; !ok && opt_.auto_evict && attempt < 4; attempt++) {
-            if (evict_lru(shard, page * 4) == 0) break;
+            if (index_.evict_lru(shard, page * 4) == 0) break;
             ok = try_alloc();
         }
         if (!ok) {
@@ -1699,19 +1386,11 @@ std::vector<RemoteBlockWire> Server::allocate_blocks(Conn* c,
         e->size = page;
         e->pool_idx = pool_idx;
         e->shard = shard;
-        e->born_sec = now_sec();
-        e->last_access.store(tick(), std::memory_order_relaxed);
+        e->born_sec = KvIndex::now_sec();
+        e->last_access.store(index_.tick(), std::memory_order_relaxed);
         Ref<BlockEntry> ref(e);
-        bool ins = false;
-        {
-            std::lock_guard<std::shared_mutex> lk(st.mu);
-            Ref<BlockEntry>* slot2 = st.map.emplace_hashed(key, h, ref, &ins);
-            if (!ins && slot2 && expired(slot2->get())) {
-                *slot2 = ref;  // expired entry: replace
-                ins = true;
-            }
-        }
-        if (!ins) {  // raced with another writer: first write wins
+        if (!index_.insert_if_absent(key, h, ref, /*replace_expired=*/true)) {
+            // raced with another writer: first write wins
             blocks.push_back({0, 0, 0});
             continue;  // `ref` releases and frees the block via ~BlockEntry
         }
@@ -1727,10 +1406,7 @@ std::vector<RemoteBlockWire> Server::allocate_blocks(Conn* c,
             vf::MrInfo mr;
             if (!vdrv_ || !vdrv_->lookup_region(ptr, &mr)) {
                 ERROR("allocate: pool arena %p has no MR on the verbs fabric", ptr);
-                {
-                    std::lock_guard<std::shared_mutex> lk(st.mu);
-                    st.map.erase(key);
-                }
+                index_.erase(key, h);
                 rollback();
                 *status = SYSTEM_ERROR;
                 return {};
@@ -1756,21 +1432,21 @@ void Server::commit_addrs(Conn* c, const std::vector<uint64_t>& addrs) {
 
 bool Server::collect_read_entries(const std::vector<std::string>& keys,
                                   std::vector<Ref<BlockEntry>>* out) {
-    out->reserve(keys.size());
-    uint64_t t = tick();
-    for (auto& key : keys) {
-        uint64_t h = KvMap::hash_of(key);
-        auto& st = kv_[stripe_of(h)];
-        std::shared_lock<std::shared_mutex> lk(st.mu);
-        Ref<BlockEntry>* v = st.map.find_hashed(key, h);
-        if (!v || !(*v)->committed || expired(v->get())) return false;
-        // fp8-compressed entries are a local-GPU-path feature: the TCP/verbs
-        // fabric moves raw bytes and cannot dequantize on the way out.
-        if ((*v)->fp8) return false;
-        (*v)->last_access.store(t, std::memory_order_relaxed);
-        out->push_back(*v);
-    }
-    return true;
+    uint64_t t = index_.tick();
+    std::vector<uint64_t> hashes(keys.size());
+    for (size_t i = 0; i < keys.size(); i++) hashes[i] = KvIndex::hash_of(keys[i]);
+    // The sweep visits keys in stripe order; `out` keeps request order.
+    out->resize(keys.size());
+    return index_.for_each_batched<KvIndex::Lock::kShared>(
+        keys.size(), hashes.data(), 0, [&](KvMap& m, size_t i) {
+            Ref<BlockEntry>* v = index_.find_live(m, keys[i], hashes[i]);
+            // fp8-compressed entries are a local-GPU-path feature: the
+            // TCP/verbs fabric moves raw bytes and cannot dequantize.
+            if (!v || !(*v)->committed || (*v)->fp8) return false;
+            (*v)->last_access.store(t, std::memory_order_relaxed);
+            (*out)[i] = *v;
+            return true;
+        });
 }
 
 void Server::op_allocate(Conn* c, const RemoteMetaMsg& msg) {
@@ -1965,15 +1641,8 @@ void Server::op_check_exist(Conn* c, const std::vector<uint8_t>& body, const Req
     // (infinistore.cpp:1078-1090).
     if (body.empty()) return reply_local(c, ctx, INVALID_REQ);
     std::string key(reinterpret_cast<const char*>(body.data()), body.size());
-    bool exists;
-    {
-        uint64_t h = KvMap::hash_of(key);
-        auto& st = kv_[stripe_of(h)];
-        std::shared_lock<std::shared_mutex> lk(st.mu);
-        Ref<BlockEntry>* v = st.map.find_hashed(key, h);
-        exists = v && (*v)->committed && !expired(v->get());
-    }
-    reply_query(c, ctx, exists ? 0 : 1);
+    Ref<BlockEntry> e = index_.lookup(key, KvIndex::hash_of(key));
+    reply_query(c, ctx, e && e->committed ? 0 : 1);
 }
 
 void Server::op_match_index(Conn* c, const std::vector<uint8_t>& body, const ReqCtx& ctx) {
@@ -1986,11 +1655,8 @@ void Server::op_match_index(Conn* c, const std::vector<uint8_t>& body, const Req
     // present (infinistore.cpp:1097); an uncommitted key cannot be read, so
     // reporting it as a hit would make the subsequent read_cache fail.
     auto present = [&](size_t i) {
-        uint64_t h = KvMap::hash_of(keys[i]);
-        auto& st = kv_[stripe_of(h)];
-        std::shared_lock<std::shared_mutex> lk(st.mu);
-        Ref<BlockEntry>* v = st.map.find_hashed(keys[i], h);
-        return v && (*v)->committed && !expired(v->get());
+        Ref<BlockEntry> e = index_.lookup(keys[i], KvIndex::hash_of(keys[i]));
+        return e && e->committed;
     };
     long left = 0, right = static_cast<long>(keys.size());
     while (left < right) {
@@ -2007,42 +1673,28 @@ void Server::op_delete(Conn* c, const std::vector<uint8_t>& body, const ReqCtx& 
     std::vector<std::string> keys;
     if (!parse_match_request(body.data(), body.size(), &keys))
         return reply_local(c, ctx, INVALID_REQ);
+    std::vector<uint64_t> hashes(keys.size());
+    for (size_t i = 0; i < keys.size(); i++) hashes[i] = KvIndex::hash_of(keys[i]);
+    std::vector<Ref<BlockEntry>> dead;  // one stripe's batch: extracted under its lock
+    // Sole-owner entries surrender their block and the blocks free in ONE
+    // allocator-lock hold per shard — per-block frees convoyed against
+    // concurrent batch allocations (1.3 s per 10k-key delete).
+    std::map<Shard*, std::vector<Shard::BlockFree>> by_shard;
     int n = 0;
-    {
-        std::array<std::vector<uint32_t>, kStripes> by_stripe;
-        std::vector<uint64_t> hashes(keys.size());
-        for (size_t i = 0; i < keys.size(); i++) {
-            hashes[i] = KvMap::hash_of(keys[i]);
-            by_stripe[stripe_of(hashes[i])].push_back(static_cast<uint32_t>(i));
-        }
-        constexpr size_t kPf = 16;
-        // Move the refs out under the lock, destroy them after unlocking:
-        // entry destruction frees pool blocks (shard alloc lock) + slab
-        // memory, which must never run under an exclusive stripe lock (it
-        // blocked every op on the stripe for ms during delete sweeps).
-        std::vector<Ref<BlockEntry>> dead;
-        dead.reserve(keys.size());
-        // Sole-owner entries surrender their block here and the blocks free
-        // in ONE allocator-lock hold per shard — per-block frees convoyed
-        // against concurrent batch allocations (1.3 s per 10k-key delete).
-        std::map<Shard*, std::vector<Shard::BlockFree>> by_shard;
-        for (size_t si = 0; si < kStripes; si++) {
-            auto& list = by_stripe[si];
-            if (list.empty()) continue;
-            {
-                std::lock_guard<std::shared_mutex> lk(kv_[si].mu);
-                auto& m = kv_[si].map;
-                for (size_t i = 0; i < std::min(kPf, list.size()); i++)
-                    m.prefetch(hashes[list[i]]);
-                for (size_t i = 0; i < list.size(); i++) {
-                    if (i + kPf < list.size()) m.prefetch(hashes[list[i + kPf]]);
-                    Ref<BlockEntry> ref;
-                    if (m.extract(keys[list[i]], &ref)) {
-                        n++;
-                        dead.emplace_back(std::move(ref));
-                    }
-                }
-            }
+    index_.for_each_batched<KvIndex::Lock::kExclusive>(
+        keys.size(), hashes.data(), 0,
+        [&](KvMap& m, size_t i) {
+            Ref<BlockEntry> ref;
+            if (m.extract(keys[i], &ref)) dead.emplace_back(std::move(ref));
+            return true;
+        },
+        nullptr,
+        [&] {
+            // Stripe released: drop its batch now, not after the whole sweep.
+            // The pause lets a reader that queued on this stripe (reads sweep
+            // from stripe 0 too) get ahead instead of trailing us for 64 locks
+            // (measured: 2 ms read-handler tails under 12-client delete churn).
+            n += static_cast<int>(dead.size());
             for (auto& ref : dead) {
                 BlockEntry* e = ref.get();
                 if (e->ref_count() == 1 && e->shard && e->ptr) {
@@ -2051,10 +1703,9 @@ void Server::op_delete(Conn* c, const std::vector<uint8_t>& body, const ReqCtx& 
                     e->ptr = nullptr;
                 }
             }
-            dead.clear();  // destructors run lock-free (per-stripe batch)
-        }
-        for (auto& [shard, frees] : by_shard) shard->deallocate_bulk(frees);
-    }
+            dead.clear();
+        });
+    for (auto& [shard, frees] : by_shard) shard->deallocate_bulk(frees);
     reply_local(c, ctx, n);
 }
 
@@ -2063,12 +1714,13 @@ void Server::op_delete(Conn* c, const std::vector<uint8_t>& body, const ReqCtx& 
 // ---------------------------------------------------------------------------
 std::pair<size_t, size_t> Server::compact() {
     if (!running_.load()) return {0, 0};
-    // Defragmentation in three phases per shard. The stripe locks are NOT
-    // held across the copy wait: a write handler holds its job's commit
-    // mutex while its insert pass takes stripe locks, and the completion
-    // thread that fulfills our copy futures can be blocked on that same
-    // commit mutex — holding the stripes here closed that into a deadlock
-    // (found by the mixed fp8/eviction soak).
+    // Defragmentation in three phases per shard. The index locks are NOT
+    // held across the copy wait: the completion threads that fulfil our
+    // copy futures also run write handlers' `fin`, and a write handler's
+    // phase D takes stripe locks while its kernel is in flight. Holding
+    // every stripe while waiting on those threads would park each writer
+    // in phase D for the whole copy with its copy slot taken, ahead of our
+    // own jobs (the mixed fp8/eviction soak deadlocked on an earlier form).
     //  1. snapshot (all stripe locks, in order): pick committed idle
     //     entries, take a Ref on each so neither delete nor eviction can
     //     free the old block mid-copy.
@@ -2082,19 +1734,13 @@ std::pair<size_t, size_t> Server::compact() {
         Shard* shard = shard_up.get();
         std::vector<Ref<BlockEntry>> held;
         std::vector<std::pair<void*, size_t>> movable;
-        {
-            std::vector<std::unique_lock<std::shared_mutex>> locks;
-            locks.reserve(kStripes);
-            for (auto& st : kv_) locks.emplace_back(st.mu);
-            for (auto& st : kv_)
-                st.map.for_each([&](std::string_view, Ref<BlockEntry>& val) {
-                    BlockEntry* e = val.get();
-                    if (e->shard == shard && e->committed && e->ref_count() == 1) {
-                        held.push_back(val);
-                        movable.push_back({e->ptr, e->size});
-                    }
-                });
-        }
+        index_.for_each_all_locked([&](std::string_view, Ref<BlockEntry>& val) {
+            BlockEntry* e = val.get();
+            if (e->shard == shard && e->committed && e->ref_count() == 1) {
+                held.push_back(val);
+                movable.push_back({e->ptr, e->size});
+            }
+        });
         if (movable.empty()) continue;
         auto moves = shard->plan_compaction(movable);
         if (moves.empty()) continue;
@@ -2120,27 +1766,21 @@ std::pair<size_t, size_t> Server::compact() {
 
         std::map<void*, Shard::Move*> by_old;
         for (auto& m : moves) by_old[m.old_ptr] = &m;
-        {
-            std::vector<std::unique_lock<std::shared_mutex>> locks;
-            locks.reserve(kStripes);
-            for (auto& st : kv_) locks.emplace_back(st.mu);
-            for (auto& st : kv_)
-                st.map.for_each([&](std::string_view, Ref<BlockEntry>& val) {
-                    BlockEntry* e = val.get();
-                    auto it = by_old.find(e->ptr);
-                    if (it == by_old.end() || e->shard != shard) return;
-                    // map ref + our `held` ref = 2; more means an in-flight
-                    // read captured the old pointer during the copy.
-                    if (!copies_ok || e->ref_count() > 2) return;
-                    Shard::Move* m = it->second;
-                    e->ptr = m->new_ptr;
-                    e->pool_idx = m->pool_idx;
-                    shard->deallocate(m->old_ptr, m->size, m->pool_idx);
-                    m->old_ptr = nullptr;  // applied
-                    moved++;
-                    bytes += m->size;
-                });
-        }
+        index_.for_each_all_locked([&](std::string_view, Ref<BlockEntry>& val) {
+            BlockEntry* e = val.get();
+            auto it = by_old.find(e->ptr);
+            if (it == by_old.end() || e->shard != shard) return;
+            // map ref + our `held` ref = 2; more means an in-flight
+            // read captured the old pointer during the copy.
+            if (!copies_ok || e->ref_count() > 2) return;
+            Shard::Move* m = it->second;
+            e->ptr = m->new_ptr;
+            e->pool_idx = m->pool_idx;
+            shard->deallocate(m->old_ptr, m->size, m->pool_idx);
+            m->old_ptr = nullptr;  // applied
+            moved++;
+            bytes += m->size;
+        });
         for (auto& m : moves)
             if (m.old_ptr != nullptr)  // unapplied: release the planned slot
                 shard->deallocate(m.new_ptr, m.size, m.pool_idx);
@@ -2148,25 +1788,6 @@ std::pair<size_t, size_t> Server::compact() {
         // (old) blocks now.
     }
     return {moved, bytes};
-}
-
-size_t Server::kvmap_len() {
-    size_t n = 0;
-    for (auto& st : kv_) {
-        std::shared_lock<std::shared_mutex> lk(st.mu);
-        n += st.map.size();
-    }
-    return n;
-}
-
-size_t Server::purge() {
-    size_t n = 0;
-    for (auto& st : kv_) {
-        std::lock_guard<std::shared_mutex> lk(st.mu);
-        n += st.map.size();
-        st.map.clear();
-    }
-    return n;
 }
 
 // ---- snapshot / restore ----------------------------------------------------
@@ -2187,13 +1808,10 @@ bool Server::snapshot(const std::string& path, std::pair<size_t, size_t>* out) {
     // make compaction skip them — it requires ref_count()==1), then stream
     // them out without holding any lock.
     std::vector<std::pair<std::string, Ref<BlockEntry>>> pinned;
-    for (auto& st : kv_) {
-        std::shared_lock<std::shared_mutex> lk(st.mu);
-        st.map.for_each([&](std::string_view key, Ref<BlockEntry>& val) {
-            if (val->committed && !expired(val.get()))
-                pinned.emplace_back(std::string(key), val);
-        });
-    }
+    index_.for_each_shared([&](std::string_view key, Ref<BlockEntry>& val) {
+        if (val->committed && !index_.expired(val.get()))
+            pinned.emplace_back(std::string(key), val);
+    });
     FILE* f = fopen(path.c_str(), "wb");
     if (!f) {
         ERROR("snapshot: cannot open %s", path.c_str());
@@ -2279,18 +1897,12 @@ bool Server::restore(const std::string& path, std::pair<size_t, size_t>* out) {
         e->shard = shard;
         e->fp8 = h.fp8 != 0;
         e->scale = h.scale;
-        e->born_sec = now_sec();
+        e->born_sec = KvIndex::now_sec();
         e->committed = true;
-        e->last_access.store(tick(), std::memory_order_relaxed);
+        e->last_access.store(index_.tick(), std::memory_order_relaxed);
         Ref<BlockEntry> ref(e);
-        uint64_t hh = KvMap::hash_of(key);
-        auto& st = kv_[stripe_of(hh)];
-        bool ins = false;
-        {
-            std::lock_guard<std::shared_mutex> lk(st.mu);
-            st.map.emplace_hashed(key, hh, ref, &ins);
-        }
-        if (ins) {
+        // Plain insert-if-absent: an expired live key still beats the snapshot.
+        if (index_.insert_if_absent(key, KvIndex::hash_of(key), ref, /*replace_expired=*/false)) {
             out->first++;
             out->second += h.size;
         }

@@ -24,7 +24,6 @@
 
 #include <uv.h>
 
-#include <array>
 #include <atomic>
 #include <condition_variable>
 #include <cstdint>
@@ -32,7 +31,6 @@
 #include <map>
 #include <memory>
 #include <mutex>
-#include <shared_mutex>
 #include <string>
 #include <string_view>
 #include <thread>
@@ -45,7 +43,7 @@
 #include "../core/utils.h"
 #include "../fabric/verbs_fabric.h"
 #include "../gpu/gpu.h"
-#include "kvmap.h"
+#include "kv_index.h"
 #include "shard.h"
 
 namespace ifs {
@@ -81,34 +79,6 @@ struct ServerOptions {
 
 class Server;
 
-// One stored block. Refcounted: the kv map holds one ref; in-flight reads
-// hold another so purge cannot free memory under an active copy.
-// Slab-allocated: prefill writes create thousands of entries per request,
-// so class-level new/delete run on a chunked freelist instead of malloc.
-struct BlockEntry : RefCounted {
-    void* ptr = nullptr;
-    size_t size = 0;
-    int pool_idx = -1;
-    Shard* shard = nullptr;
-    bool committed = false;
-    // fp8-compressed page (extension): `size` is the STORED byte size
-    // (half the logical bf16 page); reads dequantize with `scale`.
-    bool fp8 = false;
-    float scale = 1.f;
-    uint32_t born_sec = 0;  // CLOCK_MONOTONIC seconds at insert (TTL)
-    // LRU tick (auto_evict); atomic: bumped under the SHARED kv lock by
-    // concurrent readers.
-    std::atomic<uint64_t> last_access{0};
-    ~BlockEntry() override {
-        if (shard && ptr) shard->deallocate(ptr, size, pool_idx);
-    }
-    static void* operator new(size_t n);
-    static void operator delete(void* p);
-    // placement forms (class-level operator new hides the global ones)
-    static void* operator new(size_t, void* p) { return p; }
-    static void operator delete(void*, void*) {}
-};
-
 class Server {
    public:
     explicit Server(const ServerOptions& opt);
@@ -121,8 +91,8 @@ class Server {
     bool running() const { return running_.load(); }
 
     // Management plane (thread-safe; callable from Python).
-    size_t kvmap_len();
-    size_t purge();
+    size_t kvmap_len() { return index_.size(); }
+    size_t purge() { return index_.clear(); }
     std::string stats_json();
     // Defragment the pools: move committed, idle blocks to lower addresses
     // using the batched copy kernel. Returns (moved_blocks, moved_bytes).
@@ -273,21 +243,6 @@ class Server {
     Shard* shard_for_device(int device);
     Shard* shard_least_used();
     void maybe_extend(Shard* s);
-    // Evict >= `bytes` of LRU committed idle entries on `shard`. Takes
-    // stripe locks itself (callers must hold none). Returns bytes freed.
-    size_t evict_lru(Shard* shard, size_t bytes);
-    void erase_entries(const std::vector<Ref<BlockEntry>>& entries);
-    uint64_t tick() { return access_tick_.fetch_add(1, std::memory_order_relaxed); }
-    static uint32_t now_sec();
-    // TTL check (lazy expiry): true when the entry is past its lifetime —
-    // lookups treat it as absent; the evictor reclaims it first.
-    bool expired(const BlockEntry* e) const {
-        return opt_.ttl_seconds > 0 &&
-               now_sec() - e->born_sec > static_cast<uint32_t>(opt_.ttl_seconds);
-    }
-    std::atomic<uint64_t> access_tick_{1};
-    std::atomic<uint64_t> n_evicted_{0};
-
     ServerOptions opt_;
     std::vector<std::unique_ptr<Shard>> shards_;
     std::unique_ptr<vf::Driver> vdrv_;  // lazy; created at first verbs handshake
@@ -310,33 +265,11 @@ class Server {
     std::mutex ttl_mu_;
     std::condition_variable ttl_cv_;
 
-    // Open-addressing key index with arena-stored keys (csrc/server/kvmap.h)
-    // — node-based maps measured ~350 µs of insert cost per 2048-key write.
-    // Striped key index: kStripes independent open-addressing maps, each
-    // with its own reader-writer lock, selected by the top bits of the wide
-    // key hash (KvMap uses the low bits for the slot). Lookups take a
-    // stripe's lock shared; inserts/erases exclusive. Concurrent writers
-    // land on different stripes and insert in parallel — a single exclusive
-    // lock measured 334 µs avg / 8.5 ms max handler time under 8-client
-    // write churn. No path ever holds two stripe locks except compact()
-    // and purge(), which take them in index order.
-    // 64 stripes: at 64 concurrent writers the insert pass takes exclusive
-    // stripe locks; 16 stripes measured multi-ms convoys under saturation.
-    static constexpr size_t kStripes = 64;
-    struct KvStripe {
-        // shared_mutex: dedup/read/query phases take it shared so the
-        // pipelined few-connection path keeps its read concurrency. The
-        // earlier "delete starvation" was NOT rwlock reader preference (a
-        // plain-mutex experiment changed nothing) — it was per-block
-        // allocator-lock frees under the stripe lock, fixed by extract +
-        // bulk free; long sweeps now hold each stripe only briefly.
-        std::shared_mutex mu;
-        KvMap map;
-        size_t evict_hand = 0;  // per-stripe clock cursor (mu held)
-    };
-    std::array<KvStripe, kStripes> kv_;
-    static size_t stripe_of(uint64_t h) { return (h >> 58) & (kStripes - 1); }
-    std::atomic<size_t> evict_stripe_rr_{0};
+    // Striped key index (csrc/server/kv_index.h): 64 stripes, each an
+    // open-addressing map behind its own reader-writer lock. Every path,
+    // purge() included, holds one stripe lock at a time; only compact()
+    // takes them all, in index order.
+    KvIndex index_;
 
     // stats
     std::atomic<uint64_t> n_writes_{0}, n_reads_{0}, n_put_{0}, n_get_{0};

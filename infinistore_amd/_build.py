@@ -28,6 +28,7 @@ SOURCES = [
     CSRC / "gpu" / "gpu.hip",
     CSRC / "fabric" / "verbs_fabric.cpp",
     CSRC / "server" / "shard.cpp",
+    CSRC / "server" / "kv_index.cpp",
     CSRC / "server" / "server.cpp",
     CSRC / "server" / "server_verbs.cpp",
     CSRC / "client" / "client.cpp",

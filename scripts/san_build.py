@@ -30,7 +30,8 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRCS = [
     "csrc/core/log.cpp", "csrc/core/protocol.cpp", "csrc/core/mempool.cpp",
     "csrc/fabric/verbs_fabric.cpp", "csrc/server/shard.cpp",
-    "csrc/server/server.cpp", "csrc/server/server_verbs.cpp",
+    "csrc/server/kv_index.cpp", "csrc/server/server.cpp",
+    "csrc/server/server_verbs.cpp",
     "csrc/client/client.cpp", "csrc/client/client_verbs.cpp",
     "csrc/pybind.cpp",
 ]

@@ -556,6 +556,46 @@ c.close()
     assert code == 0
 
 
+@pytest.mark.parametrize("transport", ["socket", "shm"])
+def test_large_batch_dedup_read_delete(gpu_server, transport, monkeypatch):
+    """One-request batches of ~32-40 keys per index stripe (the prefetch
+    look-ahead runs): first write wins against a second write of other data,
+    new keys in that second write land, everything reads back exactly, and
+    delete / read-after-delete / check_exist agree. Over both transports."""
+    if transport == "socket":
+        monkeypatch.setenv("IFS_NO_SHM", "1")
+    conn = local_conn(gpu_server)
+    try:
+        assert conn.conn.shm_active() == (transport == "shm")
+        page = 1024  # fp32 elements: 4 KB pages
+        n_old, n_new = 2048, 512
+        n_all = n_old + n_new
+        pre = uuid.uuid4().hex
+        keys = [f"{pre}-{i}" for i in range(n_all)]
+        offs = [i * page for i in range(n_all)]
+        first = torch.randn(n_all * page, device="cuda:0")
+        second = torch.randn(n_all * page, device="cuda:0")
+        conn.local_gpu_write_cache(first, list(zip(keys[:n_old], offs[:n_old])), page)
+        conn.sync()
+        conn.local_gpu_write_cache(second, list(zip(keys, offs)), page)
+        conn.sync()
+        dst = torch.zeros_like(first)
+        conn.read_cache(dst, list(zip(keys, offs)), page)
+        conn.sync()
+        assert torch.equal(dst[: n_old * page], first[: n_old * page])  # old keys keep first data
+        assert torch.equal(dst[n_old * page:], second[n_old * page:])  # new keys hold new data
+
+        gone, kept = keys[::2], keys[1::2]
+        assert conn.delete_keys(gone) == len(gone)
+        with pytest.raises(Exception, match="-404"):  # KEY_NOT_FOUND
+            conn.read_cache(dst, [(gone[0], 0)], page)
+        assert not conn.check_exist(gone[0]) and not conn.check_exist(gone[-1])
+        assert conn.check_exist(kept[0]) and conn.check_exist(kept[-1])
+        assert conn.delete_keys(kept) == len(kept)  # leave the shared pool as found
+    finally:
+        conn.close()
+
+
 def test_ticketed_async_reads(gpu_server):
     """read_pages_async/wait_read: multiple reads in flight on one conn,
     responses consumed out of submission order."""
