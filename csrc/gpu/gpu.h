@@ -99,8 +99,11 @@ bool launch_copy_blocks_inline(int dev, Stream s, const uint64_t* src_ptrs,
                                const uint64_t* dst_ptrs, int n_blocks, size_t bytes_per_block);
 
 // --- fp8 KV compression ------------------------------------------------------
-// Quantize n blocks of bf16 (elems_per_block each) into fp8 e4m3 blocks of
-// half the byte size; one scale (absmax/448) per block -> dev_scales[i].
+// Quantize n blocks of bf16 (elems_per_block each) into fp8 e4m3fn blocks of
+// half the byte size; one scale (finite absmax/448) per block ->
+// dev_scales[i]. The codec itself is fp8_codec.h. Both kernels move 16 bytes
+// per lane: elems_per_block % 8 == 0 (checked here) and every block pointer
+// 16-byte aligned (the CALLER checks: the descriptors may be device memory).
 bool launch_quant_blocks(int dev, Stream s, const uint64_t* dev_src_ptrs,
                          const uint64_t* dev_dst_ptrs, float* dev_scales, int n_blocks,
                          size_t elems_per_block);

@@ -15,6 +15,7 @@
 #include <mutex>
 
 #include "../core/log.h"
+#include "fp8_codec.h"
 
 namespace ifs {
 namespace gpu {
@@ -375,96 +376,66 @@ bool launch_copy_blocks(int dev, Stream stream, const uint64_t* dev_src_ptrs,
 
 // --- fp8 KV-cache compression ----------------------------------------------
 // MI355X-native extension (no reference equivalent): pages enter the pool
-// quantized bf16 -> OCP fp8 e4m3 with ONE power-agnostic scale per page
-// (absmax/448), halving HBM footprint per cached page; reads dequantize
+// quantized bf16 -> OCP fp8 e4m3fn with ONE scale per page (finite
+// absmax/448), halving HBM footprint per cached page; reads dequantize
 // back to bf16 on the way out. Both kernels are memory-bound streaming
 // passes: one 512-thread workgroup per page, vectorized 8-elems-per-lane.
-// Encoding is done in integer bit math (round-to-nearest-even on the
-// normal path) so results match torch.float8_e4m3fn casts to 1 ulp.
+// The scalar codec lives in fp8_codec.h (shared with the host, where it is
+// tested exhaustively): integer bit math, round-to-nearest-even in the
+// normal AND subnormal range, so stored codes equal
+// torch.clamp(x/scale, -448, 448).to(torch.float8_e4m3fn) bit for bit; NaN
+// keeps the format's NaN code, +-inf saturates to +-448 and neither takes
+// part in the scale (docs/design.md, "fp8 page codec").
+// Both kernels issue 16-byte accesses on the bf16 side and 8-byte accesses
+// on the fp8 side: callers guarantee 16-byte-aligned block pointers.
 
-__device__ __forceinline__ uint8_t f32_to_e4m3(float f) {
-    uint32_t bits = __float_as_uint(f);
-    uint8_t sign = static_cast<uint8_t>((bits >> 24) & 0x80);
-    uint32_t u = bits & 0x7fffffffu;
-    if (u >= 0x43e00000u) return sign | 0x7e;  // |x| >= 448 -> clamp to max
-    int e = static_cast<int>(u >> 23) - 127;
-    if (e < -6) {  // subnormal region: unit 2^-9
-        if (e < -10) return sign;  // rounds to zero
-        uint32_t full = 0x800000u | (u & 0x7fffffu);  // 1.m (24-bit)
-        int shift = 23 - (e + 9);                     // 2^-9 units
-        uint32_t half = 1u << (shift - 1);
-        uint32_t q = (full + half) >> shift;          // round half away
-        if (q > 8) q = 8;                             // 8 == min normal code
-        return sign | static_cast<uint8_t>(q);
-    }
-    // RNE at mantissa bit 20.
-    uint32_t rounded = u + 0x0007ffffu + ((u >> 20) & 1u);
-    if (rounded >= 0x43e00000u) return sign | 0x7e;
-    e = static_cast<int>(rounded >> 23) - 127;
-    uint32_t m = (rounded >> 20) & 7u;
-    return sign | static_cast<uint8_t>(((e + 7) << 3) | m);
-}
-
-__device__ __forceinline__ float e4m3_to_f32(uint8_t v) {
-    uint32_t e = (v >> 3) & 0xfu;
-    uint32_t m = v & 7u;
-    float mag;
-    if (e == 0)
-        mag = static_cast<float>(m) * 0.001953125f;  // m * 2^-9
-    else
-        mag = __uint_as_float(((e - 7 + 127) << 23) | (m << 20));
-    return (v & 0x80) ? -mag : mag;
-}
-
-// One workgroup per page. Pass 1: workgroup absmax (wavefront shuffle
-// reduce + LDS). Pass 2: scale + convert, 8 bf16 in (one uint4) -> 8 fp8
-// out (one uint2) per lane per iteration.
+// One workgroup per page. Pass 1: workgroup absmax over the finite elements
+// (wavefront shuffle reduce + LDS). Pass 2: scale + convert, 8 bf16 in (one
+// uint4) -> 8 fp8 out (one uint2) per lane per iteration.
 __global__ void quant_blocks_bf16_fp8_kernel(const uint64_t* __restrict__ src_ptrs,
                                              const uint64_t* __restrict__ dst_ptrs,
                                              float* __restrict__ scales,
                                              uint64_t elems_per_block) {
     const uint16_t* src = reinterpret_cast<const uint16_t*>(src_ptrs[blockIdx.x]);
     uint8_t* dst = reinterpret_cast<uint8_t*>(dst_ptrs[blockIdx.x]);
-    __shared__ float red[8];  // 512 threads / 64-wide wavefronts
-    float m = 0.f;
+    __shared__ uint32_t red[8];  // 512 threads / 64-wide wavefronts
+    __shared__ float scale_sh;
+    uint32_t m = 0;  // largest finite bf16 magnitude, as bits
     uint64_t n8 = elems_per_block / 8;
     const uint4* src4 = reinterpret_cast<const uint4*>(src);
     for (uint64_t u = threadIdx.x; u < n8; u += blockDim.x) {
         uint4 pk = src4[u];
         const uint16_t* h = reinterpret_cast<const uint16_t*>(&pk);
 #pragma unroll
-        for (int i = 0; i < 8; i++) {
-            // bf16 absmax == f32 absmax of the widened bits.
-            float f = __uint_as_float(static_cast<uint32_t>(h[i]) << 16);
-            m = fmaxf(m, fabsf(f));
-        }
+        for (int i = 0; i < 8; i++) m = fp8::absmax_step(m, h[i]);
     }
-    for (int off = 32; off; off >>= 1) m = fmaxf(m, __shfl_down(m, off, 64));
+    for (int off = 32; off; off >>= 1) m = max(m, __shfl_down(m, off, 64));
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
     __syncthreads();
     if (threadIdx.x == 0) {
-        float mm = red[0];
-        for (int w = 1; w < static_cast<int>(blockDim.x) / 64; w++) mm = fmaxf(mm, red[w]);
-        red[0] = mm > 0.f ? mm / 448.f : 1.f;  // scale
-        scales[blockIdx.x] = red[0];
+        uint32_t mm = red[0];
+        for (int w = 1; w < static_cast<int>(blockDim.x) / 64; w++) mm = max(mm, red[w]);
+        scale_sh = fp8::scale_from_absmax_bits(mm);
+        scales[blockIdx.x] = scale_sh;
     }
     __syncthreads();
-    float inv = 1.f / red[0];
+    float inv = 1.f / scale_sh;
     for (uint64_t u = threadIdx.x; u < n8; u += blockDim.x) {
         uint4 pk = src4[u];
         const uint16_t* h = reinterpret_cast<const uint16_t*>(&pk);
         uint8_t out[8];
 #pragma unroll
         for (int i = 0; i < 8; i++) {
-            float f = __uint_as_float(static_cast<uint32_t>(h[i]) << 16);
-            out[i] = f32_to_e4m3(f * inv);
+            float f = fp8::bits_f32(static_cast<uint32_t>(h[i]) << 16);
+            out[i] = fp8::f32_to_e4m3(f * inv);
         }
         reinterpret_cast<uint2*>(dst)[u] = *reinterpret_cast<const uint2*>(out);
     }
 }
 
-// Dequantize fp8 pages back into bf16 client memory (round-to-nearest-even
-// bf16 truncation): 8 fp8 in (uint2) -> 8 bf16 out (uint4) per lane.
+// Dequantize fp8 pages back into bf16 client memory (value * scale in fp32,
+// round-to-nearest-even to bf16): 8 fp8 in (uint2) -> 8 bf16 out (uint4)
+// per lane.
 __global__ void dequant_blocks_fp8_bf16_kernel(const uint64_t* __restrict__ src_ptrs,
                                                const uint64_t* __restrict__ dst_ptrs,
                                                const float* __restrict__ scales,
@@ -478,12 +449,7 @@ __global__ void dequant_blocks_fp8_bf16_kernel(const uint64_t* __restrict__ src_
         const uint8_t* b = reinterpret_cast<const uint8_t*>(&pk);
         uint16_t out[8];
 #pragma unroll
-        for (int i = 0; i < 8; i++) {
-            float f = e4m3_to_f32(b[i]) * scale;
-            uint32_t fb = __float_as_uint(f);
-            fb += 0x7fffu + ((fb >> 16) & 1u);  // RNE to bf16
-            out[i] = static_cast<uint16_t>(fb >> 16);
-        }
+        for (int i = 0; i < 8; i++) out[i] = fp8::decode_to_bf16(b[i], scale);
         reinterpret_cast<uint4*>(dst)[u] = *reinterpret_cast<const uint4*>(out);
     }
 }
@@ -532,9 +498,23 @@ __global__ void hash_blocks_kernel(const uint64_t* __restrict__ ptrs, uint64_t b
     const uint8_t* base = reinterpret_cast<const uint8_t*>(ptrs[blk]);
     uint64_t n_words = bytes_per_block / 8;
     uint64_t h = 0;
-    const uint64_t* w = reinterpret_cast<const uint64_t*>(base);
-    for (uint64_t i = threadIdx.x; i < n_words; i += blockDim.x) {
-        h ^= mix64(w[i] ^ (i * 0xff51afd7ed558ccdull));
+    // The fingerprint is defined over BYTES (little-endian 8-byte words), so
+    // it must not depend on where the block starts. 8-byte loads need an
+    // 8-byte-aligned base; any other base assembles each word from byte
+    // loads. `base` comes from the descriptor, so the branch is uniform
+    // across the workgroup.
+    if ((reinterpret_cast<uint64_t>(base) & 7u) == 0) {
+        const uint64_t* w = reinterpret_cast<const uint64_t*>(base);
+        for (uint64_t i = threadIdx.x; i < n_words; i += blockDim.x)
+            h ^= mix64(w[i] ^ (i * 0xff51afd7ed558ccdull));
+    } else {
+        for (uint64_t i = threadIdx.x; i < n_words; i += blockDim.x) {
+            uint64_t word = 0;
+#pragma unroll
+            for (int k = 0; k < 8; k++)
+                word |= static_cast<uint64_t>(base[i * 8 + k]) << (8 * k);
+            h ^= mix64(word ^ (i * 0xff51afd7ed558ccdull));
+        }
     }
     // Tail bytes (thread 0 only).
     if (threadIdx.x == 0) {

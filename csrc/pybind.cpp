@@ -18,6 +18,7 @@
 #include "fabric/wr_flow.h"
 #include "core/protocol.h"
 #include "core/mempool.h"
+#include "gpu/fp8_codec.h"
 #include "gpu/gpu.h"
 #include "server/server.h"
 
@@ -109,22 +110,146 @@ std::vector<uint64_t> hash_blocks_py(uintptr_t base, std::vector<uint64_t> offse
                                      size_t block_size, int device) {
     size_t n = offsets.size();
     std::vector<uint64_t> out(n, 0);
-    if (!gpu::available() || n == 0) return out;
+    if (n == 0) return out;
+    if (!gpu::available()) throw std::runtime_error("hash_blocks: no GPU available");
     std::vector<uint64_t> ptrs(n);
     for (size_t i = 0; i < n; i++) ptrs[i] = base + offsets[i];
-    gpu::set_device(device);
     auto* d_ptrs = static_cast<uint64_t*>(gpu::alloc_device(device, n * 8));
     auto* d_out = static_cast<uint64_t*>(gpu::alloc_device(device, n * 8));
-    if (!d_ptrs || !d_out) return out;
-    gpu::Stream s = gpu::stream_create(device);
-    gpu::memcpy_h2d(d_ptrs, ptrs.data(), n * 8);
-    gpu::launch_hash_blocks(device, s, d_ptrs, static_cast<int>(n), block_size, d_out);
-    gpu::stream_sync(s);
-    gpu::memcpy_d2h(out.data(), d_out, n * 8);
+    gpu::Stream s = d_ptrs && d_out ? gpu::stream_create(device) : nullptr;
+    bool ok = s && gpu::memcpy_h2d(d_ptrs, ptrs.data(), n * 8) &&
+              gpu::launch_hash_blocks(device, s, d_ptrs, static_cast<int>(n), block_size,
+                                      d_out) &&
+              gpu::stream_sync(s) && gpu::memcpy_d2h(out.data(), d_out, n * 8);
+    std::string err = ok ? "" : gpu::last_error();
     gpu::stream_destroy(s);
     gpu::free_device(d_ptrs);
     gpu::free_device(d_out);
+    if (!ok) throw std::runtime_error("hash_blocks failed: " + err);
     return out;
+}
+
+// ---- direct kernel entry points (debug/test surface) ----------------------
+// Descriptors and scales sit in pinned host memory exactly as in
+// Shard::submit_copy, so a test that goes through these runs what production
+// runs. Every request the kernel cannot serve is refused before any launch.
+
+// Pinned host array, freed on scope exit.
+template <typename T>
+struct Pinned {
+    T* p;
+    explicit Pinned(size_t n) : p(static_cast<T*>(gpu::alloc_host_pinned(n * sizeof(T)))) {
+        if (!p) throw std::runtime_error("alloc_host_pinned failed");
+    }
+    ~Pinned() { gpu::free_host_pinned(p); }
+    Pinned(const Pinned&) = delete;
+    Pinned& operator=(const Pinned&) = delete;
+};
+
+struct ScopedStream {
+    gpu::Stream s;
+    explicit ScopedStream(int device) : s(gpu::stream_create(device)) {
+        if (!s) throw std::runtime_error("stream_create failed");
+    }
+    ~ScopedStream() { gpu::stream_destroy(s); }
+    ScopedStream(const ScopedStream&) = delete;
+    ScopedStream& operator=(const ScopedStream&) = delete;
+};
+
+void require_gpu_and_pairs(const char* what, const std::vector<uint64_t>& src,
+                           const std::vector<uint64_t>& dst) {
+    if (!gpu::available()) throw std::runtime_error(std::string(what) + ": no GPU available");
+    if (src.size() != dst.size())
+        throw std::invalid_argument(std::string(what) + ": src/dst length mismatch");
+    if (src.size() > static_cast<size_t>(INT32_MAX))
+        throw std::invalid_argument(std::string(what) + ": too many blocks");
+}
+
+bool all_aligned16(const std::vector<uint64_t>& a, const std::vector<uint64_t>& b) {
+    for (uint64_t p : a)
+        if (p % 16) return false;
+    for (uint64_t p : b)
+        if (p % 16) return false;
+    return true;
+}
+
+void copy_blocks_py(const std::vector<uint64_t>& src, const std::vector<uint64_t>& dst,
+                    size_t bytes_per_block, int device, const std::string& path) {
+    require_gpu_and_pairs("_dbg_copy_blocks", src, dst);
+    const bool vec = path == "vec", inl = path == "inline";
+    if (!vec && !inl && path != "byte")
+        throw std::invalid_argument("_dbg_copy_blocks: path must be vec, byte or inline");
+    if (bytes_per_block == 0) throw std::invalid_argument("_dbg_copy_blocks: empty blocks");
+    if ((vec || inl) && (bytes_per_block % 16 != 0 || !all_aligned16(src, dst)))
+        throw std::invalid_argument("_dbg_copy_blocks: " + path +
+                                    " path needs 16-byte-aligned pointers and size");
+    if (inl && src.size() > 16)
+        throw std::invalid_argument("_dbg_copy_blocks: inline path takes at most 16 blocks");
+    size_t n = src.size();
+    if (n == 0) return;
+    Pinned<uint64_t> h_src(n), h_dst(n);
+    memcpy(h_src.p, src.data(), n * 8);
+    memcpy(h_dst.p, dst.data(), n * 8);
+    ScopedStream st(device);
+    bool ok = inl ? gpu::launch_copy_blocks_inline(device, st.s, h_src.p, h_dst.p,
+                                                   static_cast<int>(n), bytes_per_block)
+                  : gpu::launch_copy_blocks(device, st.s, h_src.p, h_dst.p,
+                                            static_cast<int>(n), bytes_per_block, vec);
+    // Always drain the stream before the pinned descriptors go away.
+    bool synced = gpu::stream_sync(st.s);
+    if (!ok || !synced)
+        throw std::runtime_error(std::string("_dbg_copy_blocks failed: ") + gpu::last_error());
+}
+
+void require_quant_shape(const char* what, const std::vector<uint64_t>& src,
+                         const std::vector<uint64_t>& dst, size_t elems_per_block) {
+    require_gpu_and_pairs(what, src, dst);
+    if (elems_per_block == 0 || elems_per_block % 8 != 0)
+        throw std::invalid_argument(std::string(what) + ": elems_per_block % 8 != 0");
+    if (!all_aligned16(src, dst))
+        throw std::invalid_argument(std::string(what) + ": pointers must be 16-byte aligned");
+}
+
+std::vector<float> quant_blocks_py(const std::vector<uint64_t>& src,
+                                   const std::vector<uint64_t>& dst, size_t elems_per_block,
+                                   int device) {
+    require_quant_shape("_dbg_quant_blocks", src, dst, elems_per_block);
+    size_t n = src.size();
+    std::vector<float> scales(n);
+    if (n == 0) return scales;
+    Pinned<uint64_t> h_src(n), h_dst(n);
+    Pinned<float> h_scale(n);
+    memcpy(h_src.p, src.data(), n * 8);
+    memcpy(h_dst.p, dst.data(), n * 8);
+    ScopedStream st(device);
+    bool ok = gpu::launch_quant_blocks(device, st.s, h_src.p, h_dst.p, h_scale.p,
+                                       static_cast<int>(n), elems_per_block);
+    bool synced = gpu::stream_sync(st.s);
+    if (!ok || !synced)
+        throw std::runtime_error(std::string("_dbg_quant_blocks failed: ") + gpu::last_error());
+    memcpy(scales.data(), h_scale.p, n * sizeof(float));
+    return scales;
+}
+
+void dequant_blocks_py(const std::vector<uint64_t>& src, const std::vector<uint64_t>& dst,
+                       const std::vector<float>& scales, size_t elems_per_block, int device) {
+    require_quant_shape("_dbg_dequant_blocks", src, dst, elems_per_block);
+    if (scales.size() != src.size())
+        throw std::invalid_argument("_dbg_dequant_blocks: one scale per block");
+    size_t n = src.size();
+    if (n == 0) return;
+    Pinned<uint64_t> h_src(n), h_dst(n);
+    Pinned<float> h_scale(n);
+    memcpy(h_src.p, src.data(), n * 8);
+    memcpy(h_dst.p, dst.data(), n * 8);
+    memcpy(h_scale.p, scales.data(), n * sizeof(float));
+    ScopedStream st(device);
+    bool ok = gpu::launch_dequant_blocks(device, st.s, h_src.p, h_dst.p, h_scale.p,
+                                         static_cast<int>(n), elems_per_block);
+    bool synced = gpu::stream_sync(st.s);
+    if (!ok || !synced)
+        throw std::runtime_error(std::string("_dbg_dequant_blocks failed: ") +
+                                 gpu::last_error());
 }
 
 }  // namespace
@@ -411,6 +536,46 @@ PYBIND11_MODULE(_native, m) {
     m.def("gpu_available", [] { return gpu::available(); });
     m.def("gpu_count", [] { return gpu::device_count(); });
     m.def("hash_blocks", &hash_blocks_py, py::call_guard<py::gil_scoped_release>());
+
+    // ---- debug/test surface (kernels, launched directly) ----
+    m.def("_dbg_copy_blocks", &copy_blocks_py, py::arg("src_ptrs"), py::arg("dst_ptrs"),
+          py::arg("bytes_per_block"), py::arg("device"), py::arg("path"),
+          py::call_guard<py::gil_scoped_release>());
+    m.def("_dbg_quant_blocks", &quant_blocks_py, py::arg("src_ptrs"), py::arg("dst_ptrs"),
+          py::arg("elems_per_block"), py::arg("device"),
+          py::call_guard<py::gil_scoped_release>());
+    m.def("_dbg_dequant_blocks", &dequant_blocks_py, py::arg("src_ptrs"), py::arg("dst_ptrs"),
+          py::arg("scales"), py::arg("elems_per_block"), py::arg("device"),
+          py::call_guard<py::gil_scoped_release>());
+
+    // ---- debug/test surface (fp8 codec on the host: csrc/gpu/fp8_codec.h) ----
+    m.def("_dbg_fp8_encode", [](py::buffer f32) {
+        py::buffer_info in = f32.request();
+        if (in.itemsize != 4 || in.format != py::format_descriptor<float>::format())
+            throw std::invalid_argument("_dbg_fp8_encode takes a float32 buffer");
+        const float* x = static_cast<const float*>(in.ptr);
+        std::string out(static_cast<size_t>(in.size), '\0');
+        for (size_t i = 0; i < out.size(); i++)
+            out[i] = static_cast<char>(fp8::f32_to_e4m3(x[i]));
+        return py::bytes(out);
+    });
+    m.def("_dbg_fp8_decode", [](py::buffer codes, float scale) {
+        py::buffer_info in = codes.request();
+        if (in.itemsize != 1) throw std::invalid_argument("_dbg_fp8_decode takes a uint8 buffer");
+        const uint8_t* c = static_cast<const uint8_t*>(in.ptr);
+        std::vector<uint16_t> out(static_cast<size_t>(in.size));
+        for (size_t i = 0; i < out.size(); i++) out[i] = fp8::decode_to_bf16(c[i], scale);
+        return py::bytes(reinterpret_cast<const char*>(out.data()), out.size() * 2);
+    });
+    m.def("_dbg_fp8_scale", [](py::buffer bf16_bits) {
+        py::buffer_info in = bf16_bits.request();
+        if (in.itemsize != 2)
+            throw std::invalid_argument("_dbg_fp8_scale takes the uint16 bits of a bf16 page");
+        const uint16_t* h = static_cast<const uint16_t*>(in.ptr);
+        uint32_t m = 0;
+        for (py::ssize_t i = 0; i < in.size; i++) m = fp8::absmax_step(m, h[i]);
+        return fp8::scale_from_absmax_bits(m);
+    });
 
     // ---- debug/test surface (wire format + mempool) ----
     m.def("_dbg_build_local_meta", [](int device, py::bytes ipc, int block_size,

@@ -754,6 +754,13 @@ void Server::op_local_write(Conn* c, const LocalView& msg, const ReqCtx& ctx) {
     // with one scale per page; requires a 16-byte-divisible page.
     const bool quant = (msg.flags & kLocalFlagQuantFp8) != 0;
     if (quant && (page % 16 != 0)) return reply_local(c, ctx, INVALID_REQ);
+    // The quantize kernel loads 16 bytes per lane: every source page must
+    // start 16-byte aligned (pool blocks always do).
+    if (quant) {
+        for (size_t i = 0; i < nb; i++)
+            if (reinterpret_cast<uintptr_t>(client_ptr + msg.blocks[i].second) % 16 != 0)
+                return reply_local(c, ctx, INVALID_REQ);
+    }
     const size_t stored = quant ? page / 2 : page;
 
     // Phase A — dedup check only (shared stripe locks, prefetch-pipelined).
@@ -992,7 +999,10 @@ void Server::op_local_read(Conn* c, const LocalView& msg, const ReqCtx& ctx) {
             }
             BlockEntry* e = v->get();
             e->last_access.store(read_tick, std::memory_order_relaxed);
-            if (e->fp8 && e->size * 2 != page) {
+            // fp8 entries: the page must be the written size, and the
+            // dequantize kernel stores 16 bytes per lane into the client.
+            if (e->fp8 && (e->size * 2 != page ||
+                           reinterpret_cast<uintptr_t>(client_ptr + b.second) % 16 != 0)) {
                 err = INVALID_REQ;
                 return false;
             }

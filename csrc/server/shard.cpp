@@ -272,6 +272,8 @@ bool Shard::submit_copy(CopyJob&& job) {
         for (size_t i = 0; i < n && aligned; i++)
             aligned = (job.src[i] % 16 == 0) && (job.dst[i] % 16 == 0);
     }
+    // The fp8 kernels have no byte fallback: they only ever run aligned.
+    if (!aligned && job.xform != CopyJob::Xform::kCopy) return false;
 
     // HIP stream enqueues are thread-safe; each job's ops precede its event
     // in stream order regardless of interleaving with other submitters, so

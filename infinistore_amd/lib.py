@@ -382,6 +382,12 @@ class InfinityConnection:
             flags = self.FLAG_QUANT_FP8
         es = cache.element_size()
         offs = np.asarray(offsets, dtype=np.uint64)
+        if quant is not None:
+            # the quantize kernel loads 16 bytes (8 bf16) per lane
+            if cache.data_ptr() % 16 != 0 or (offs % np.uint64(8)).any():
+                raise ValueError(
+                    "fp8 quant needs a 16-byte-aligned cache and page offsets "
+                    "that are multiples of 8 elements")
         if isinstance(keys, (bytes, bytearray, memoryview)):
             ret = self.conn.rw_local_blob(
                 self.OP_W, keys, offs, es, page_size * es,

@@ -15,6 +15,13 @@ import torch
 
 import infinistore_amd as ifs
 
+from _kernel_refs import (
+    assert_bf16_bits_equal,
+    bf16_bits,
+    fingerprint_ref as _fingerprint_ref,
+    fp8_dequant_ref,
+    fp8_quant_ref,
+)
 from conftest import free_port, make_client
 
 pytestmark = pytest.mark.gpu
@@ -217,33 +224,6 @@ def test_fabric_staged_multichunk_roundtrip(gpu_server):
         assert torch.equal(src, dst)
     finally:
         conn.close()
-
-
-def _mix64(x):
-    M = (1 << 64) - 1
-    x = (x + 0x9E3779B97F4A7C15) & M
-    x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & M
-    x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & M
-    return x ^ (x >> 31)
-
-
-def _fingerprint_ref(data: bytes, block_size: int):
-    """Pure-Python reference of the hash_blocks kernel."""
-    M = (1 << 64) - 1
-    out = []
-    for b0 in range(0, len(data), block_size):
-        blk = data[b0 : b0 + block_size]
-        h = 0
-        nw = len(blk) // 8
-        for i in range(nw):
-            w = int.from_bytes(blk[i * 8 : i * 8 + 8], "little")
-            h ^= _mix64(w ^ ((i * 0xFF51AFD7ED558CCD) & M))
-        tb = len(blk) - nw * 8
-        if tb:
-            tail = int.from_bytes(blk[nw * 8 :], "little")
-            h ^= _mix64(tail ^ ((nw * 0xFF51AFD7ED558CCD) & M))
-        out.append(_mix64(h ^ block_size))
-    return out
 
 
 def test_fingerprint_kernel_vs_cpu_reference():
@@ -665,16 +645,13 @@ def test_fp8_quantized_pages(gpu_server):
         p_blocks = stats2["used_blocks"] - stats1["used_blocks"]
         assert q_blocks * 2 == p_blocks, (q_blocks, p_blocks)
 
+        # bit-exact against the shared codec reference (tests/_kernel_refs.py)
+        ref_codes, ref_scales = fp8_quant_ref(src.cpu().reshape(n, page_elems))
+        assert_bf16_bits_equal(bf16_bits(dst),
+                               bf16_bits(fp8_dequant_ref(ref_codes, ref_scales)))
         for i in range(n):
             page = src[offs[i] : offs[i] + page_elems].float()
-            scale = page.abs().max().item() / 448.0 or 1.0
-            ref = ((page / scale).to(torch.float8_e4m3fn).float() * scale
-                   ).to(torch.bfloat16).float()
             got = dst[offs[i] : offs[i] + page_elems].float()
-            # normal-path RNE matches torch exactly; allow one subnormal ulp
-            # plus bf16 rounding at the edges
-            diff = (got - ref).abs().max().item()
-            assert diff <= scale * 2 ** -6, (i, diff, scale)
             # end-to-end error vs the original bf16 page: fp8 mantissa step
             rel = (got - page).abs().max().item() / page.abs().max().item()
             assert rel <= 0.07, (i, rel)
