@@ -84,6 +84,10 @@ constexpr uint32_t kLocalFlagSyncResponse = 1;
 // half the HBM per cached page; reads dequantize transparently (extension,
 // csrc/gpu/gpu.hip quant kernels).
 constexpr uint32_t kLocalFlagQuantFp8 = 2;
+// Store the (bf16) payload as OCP MXFP4: e2m1 codes plus one e8m0 scale per
+// 32 elements inside the stored block, 17/64 of the bf16 bytes (extension,
+// csrc/gpu/mxfp4_codec.h). Setting both quant flags is INVALID_REQ.
+constexpr uint32_t kLocalFlagQuantMxfp4 = 4;
 
 std::string op_name(char op);
 

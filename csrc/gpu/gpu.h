@@ -112,6 +112,24 @@ bool launch_dequant_blocks(int dev, Stream s, const uint64_t* dev_src_ptrs,
                            const uint64_t* dev_dst_ptrs, const float* dev_scales, int n_blocks,
                            size_t elems_per_block);
 
+// --- mxfp4 KV compression ----------------------------------------------------
+// Quantize n blocks of bf16 (elems_per_block each) into OCP MXFP4 blocks of
+// elems/2 + elems/32 bytes: e2m1 codes, two per byte, then one e8m0 scale
+// byte per 32 elements. The scales live inside the block, so there is no
+// scale array. The codec itself is mxfp4_codec.h. elems_per_block % 32 == 0
+// (checked here); every block pointer 16-byte aligned (the CALLER checks:
+// the descriptors may be device memory).
+bool launch_quant_blocks_mxfp4(int dev, Stream s, const uint64_t* dev_src_ptrs,
+                               const uint64_t* dev_dst_ptrs, int n_blocks,
+                               size_t elems_per_block);
+// Inverse: mxfp4 blocks -> bf16 blocks.
+bool launch_dequant_blocks_mxfp4(int dev, Stream s, const uint64_t* dev_src_ptrs,
+                                 const uint64_t* dev_dst_ptrs, int n_blocks,
+                                 size_t elems_per_block);
+// Groups of 32 elements that one workgroup of either mxfp4 kernel covers per
+// loop iteration (four lanes per group).
+constexpr int kMxfp4GroupsPerIter = 64;
+
 // --- block fingerprint ------------------------------------------------------
 // 64-bit position-salted fingerprint per block -> out_hashes[i] (device mem).
 bool launch_hash_blocks(int dev, Stream s, const uint64_t* dev_ptrs, int n_blocks,

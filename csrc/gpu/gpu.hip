@@ -16,6 +16,7 @@
 
 #include "../core/log.h"
 #include "fp8_codec.h"
+#include "mxfp4_codec.h"
 
 namespace ifs {
 namespace gpu {
@@ -478,6 +479,122 @@ bool launch_dequant_blocks(int dev, Stream stream, const uint64_t* dev_src_ptrs,
                        dev_src_ptrs, dev_dst_ptrs, dev_scales, elems_per_block);
     HIP_OK(hipGetLastError());
     return true;
+}
+
+// --- mxfp4 KV-cache compression ---------------------------------------------
+// bf16 pages <-> OCP microscaling FP4: e2m1 codes, two per byte, followed by
+// one e8m0 scale byte per group of 32 elements (block layout and rules:
+// docs/design.md, "mxfp4 page codec"; scalar codec: mxfp4_codec.h). A scale
+// covers 32 neighbouring elements only, so there is no page-wide reduction
+// and each kernel is ONE streaming pass that touches every byte once. Four
+// lanes share a group: on the bf16 side a lane moves one uint4 (8 elements),
+// so a wave's accesses stay fully coalesced 16-byte ones; on the stored side
+// it moves the 4 bytes holding its 8 codes. Work is laid out like the copy
+// kernel's: workgroup (b, chunk), descriptor read once through LDS, so a
+// request of few pages still fills the device.
+// elems_per_block % 32 == 0 makes the lane-unit count a multiple of 4, and
+// chunk * blockDim.x and the stride are multiples of 4 too: the four lanes of
+// a quad always run the loop body together, and the cross-lane steps below
+// only ever read lanes of the own quad.
+constexpr int kMxfp4Threads = 4 * kMxfp4GroupsPerIter;
+
+__global__ void quant_blocks_bf16_mxfp4_kernel(const uint64_t* __restrict__ src_ptrs,
+                                               const uint64_t* __restrict__ dst_ptrs,
+                                               uint32_t chunks_per_block,
+                                               uint64_t elems_per_block) {
+    uint32_t b = blockIdx.x / chunks_per_block;
+    uint32_t chunk = blockIdx.x % chunks_per_block;
+    __shared__ uint64_t sd[2];
+    if (threadIdx.x == 0) {
+        sd[0] = src_ptrs[b];
+        sd[1] = dst_ptrs[b];
+    }
+    __syncthreads();
+    const uint4* src4 = reinterpret_cast<const uint4*>(sd[0]);
+    uint32_t* codes = reinterpret_cast<uint32_t*>(sd[1]);
+    uint8_t* scales = reinterpret_cast<uint8_t*>(sd[1]) + elems_per_block / 2;
+    uint64_t n8 = elems_per_block / 8;
+    uint64_t stride = static_cast<uint64_t>(chunks_per_block) * blockDim.x;
+    for (uint64_t u = static_cast<uint64_t>(chunk) * blockDim.x + threadIdx.x; u < n8;
+         u += stride) {
+        uint4 pk = src4[u];
+        const uint16_t* h = reinterpret_cast<const uint16_t*>(&pk);
+        uint32_t key = 0;
+#pragma unroll
+        for (int i = 0; i < 8; i++) key = mxfp4::key_step(key, h[i]);
+        key = max(key, __shfl_xor(key, 1, 64));
+        key = max(key, __shfl_xor(key, 2, 64));
+        uint8_t E = mxfp4::group_exponent(key);
+        uint32_t out = 0;
+#pragma unroll
+        for (int i = 0; i < 8; i++)
+            out |= static_cast<uint32_t>(mxfp4::encode(h[i], E)) << (4 * i);
+        codes[u] = out;
+        if ((u & 3u) == 0) scales[u >> 2] = E;
+    }
+}
+
+__global__ void dequant_blocks_mxfp4_bf16_kernel(const uint64_t* __restrict__ src_ptrs,
+                                                 const uint64_t* __restrict__ dst_ptrs,
+                                                 uint32_t chunks_per_block,
+                                                 uint64_t elems_per_block) {
+    uint32_t b = blockIdx.x / chunks_per_block;
+    uint32_t chunk = blockIdx.x % chunks_per_block;
+    __shared__ uint64_t sd[2];
+    if (threadIdx.x == 0) {
+        sd[0] = src_ptrs[b];
+        sd[1] = dst_ptrs[b];
+    }
+    __syncthreads();
+    const uint32_t* codes = reinterpret_cast<const uint32_t*>(sd[0]);
+    const uint8_t* scales = reinterpret_cast<const uint8_t*>(sd[0]) + elems_per_block / 2;
+    uint4* dst4 = reinterpret_cast<uint4*>(sd[1]);
+    uint64_t n8 = elems_per_block / 8;
+    uint64_t stride = static_cast<uint64_t>(chunks_per_block) * blockDim.x;
+    for (uint64_t u = static_cast<uint64_t>(chunk) * blockDim.x + threadIdx.x; u < n8;
+         u += stride) {
+        uint32_t pk = codes[u];
+        uint8_t E = scales[u >> 2];  // the quad's four lanes read the same byte
+        uint16_t out[8];
+#pragma unroll
+        for (int i = 0; i < 8; i++)
+            out[i] = mxfp4::decode(static_cast<uint8_t>((pk >> (4 * i)) & 0xfu), E);
+        dst4[u] = *reinterpret_cast<const uint4*>(out);
+    }
+}
+
+static bool launch_mxfp4(bool quant, int dev, Stream stream, const uint64_t* dev_src_ptrs,
+                         const uint64_t* dev_dst_ptrs, int n_blocks, size_t elems_per_block) {
+    if (n_blocks <= 0) return true;
+    if (elems_per_block == 0 || elems_per_block % mxfp4::kGroupElems != 0) return false;
+    HIP_OK(hipSetDevice(dev));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    uint32_t chunks = copy_chunks_per_block(elems_per_block / 8, n_blocks, kMxfp4Threads);
+    dim3 grid(static_cast<uint32_t>(n_blocks) * chunks);
+    if (quant)
+        hipLaunchKernelGGL(quant_blocks_bf16_mxfp4_kernel, grid, dim3(kMxfp4Threads), 0, s,
+                           dev_src_ptrs, dev_dst_ptrs, chunks,
+                           static_cast<uint64_t>(elems_per_block));
+    else
+        hipLaunchKernelGGL(dequant_blocks_mxfp4_bf16_kernel, grid, dim3(kMxfp4Threads), 0, s,
+                           dev_src_ptrs, dev_dst_ptrs, chunks,
+                           static_cast<uint64_t>(elems_per_block));
+    HIP_OK(hipGetLastError());
+    return true;
+}
+
+bool launch_quant_blocks_mxfp4(int dev, Stream stream, const uint64_t* dev_src_ptrs,
+                               const uint64_t* dev_dst_ptrs, int n_blocks,
+                               size_t elems_per_block) {
+    return launch_mxfp4(true, dev, stream, dev_src_ptrs, dev_dst_ptrs, n_blocks,
+                        elems_per_block);
+}
+
+bool launch_dequant_blocks_mxfp4(int dev, Stream stream, const uint64_t* dev_src_ptrs,
+                                 const uint64_t* dev_dst_ptrs, int n_blocks,
+                                 size_t elems_per_block) {
+    return launch_mxfp4(false, dev, stream, dev_src_ptrs, dev_dst_ptrs, n_blocks,
+                        elems_per_block);
 }
 
 // --- fingerprint -----------------------------------------------------------

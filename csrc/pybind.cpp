@@ -19,6 +19,7 @@
 #include "core/protocol.h"
 #include "core/mempool.h"
 #include "gpu/fp8_codec.h"
+#include "gpu/mxfp4_codec.h"
 #include "gpu/gpu.h"
 #include "server/server.h"
 
@@ -250,6 +251,31 @@ void dequant_blocks_py(const std::vector<uint64_t>& src, const std::vector<uint6
     if (!ok || !synced)
         throw std::runtime_error(std::string("_dbg_dequant_blocks failed: ") +
                                  gpu::last_error());
+}
+
+// mxfp4: the scales live inside the stored block, so both directions take
+// pointer lists only.
+void mxfp4_blocks_py(bool quant, const std::vector<uint64_t>& src,
+                     const std::vector<uint64_t>& dst, size_t elems_per_block, int device) {
+    const char* what = quant ? "_dbg_mxfp4_quant_blocks" : "_dbg_mxfp4_dequant_blocks";
+    require_gpu_and_pairs(what, src, dst);
+    if (elems_per_block == 0 || elems_per_block % mxfp4::kGroupElems != 0)
+        throw std::invalid_argument(std::string(what) + ": elems_per_block % 32 != 0");
+    if (!all_aligned16(src, dst))
+        throw std::invalid_argument(std::string(what) + ": pointers must be 16-byte aligned");
+    size_t n = src.size();
+    if (n == 0) return;
+    Pinned<uint64_t> h_src(n), h_dst(n);
+    memcpy(h_src.p, src.data(), n * 8);
+    memcpy(h_dst.p, dst.data(), n * 8);
+    ScopedStream st(device);
+    bool ok = quant ? gpu::launch_quant_blocks_mxfp4(device, st.s, h_src.p, h_dst.p,
+                                                     static_cast<int>(n), elems_per_block)
+                    : gpu::launch_dequant_blocks_mxfp4(device, st.s, h_src.p, h_dst.p,
+                                                       static_cast<int>(n), elems_per_block);
+    bool synced = gpu::stream_sync(st.s);
+    if (!ok || !synced)
+        throw std::runtime_error(std::string(what) + " failed: " + gpu::last_error());
 }
 
 }  // namespace
@@ -575,6 +601,59 @@ PYBIND11_MODULE(_native, m) {
         uint32_t m = 0;
         for (py::ssize_t i = 0; i < in.size; i++) m = fp8::absmax_step(m, h[i]);
         return fp8::scale_from_absmax_bits(m);
+    });
+
+    // ---- debug/test surface (mxfp4 kernels, and the codec on the host:
+    // csrc/gpu/mxfp4_codec.h) ----
+    m.def("_dbg_mxfp4_quant_blocks",
+          [](const std::vector<uint64_t>& src, const std::vector<uint64_t>& dst,
+             size_t elems_per_block, int device) {
+              mxfp4_blocks_py(true, src, dst, elems_per_block, device);
+          },
+          py::arg("src_ptrs"), py::arg("dst_ptrs"), py::arg("elems_per_block"),
+          py::arg("device"), py::call_guard<py::gil_scoped_release>());
+    m.def("_dbg_mxfp4_dequant_blocks",
+          [](const std::vector<uint64_t>& src, const std::vector<uint64_t>& dst,
+             size_t elems_per_block, int device) {
+              mxfp4_blocks_py(false, src, dst, elems_per_block, device);
+          },
+          py::arg("src_ptrs"), py::arg("dst_ptrs"), py::arg("elems_per_block"),
+          py::arg("device"), py::call_guard<py::gil_scoped_release>());
+    m.attr("_MXFP4_GROUPS_PER_ITER") = gpu::kMxfp4GroupsPerIter;
+    // Scale byte E of ONE group: the uint16 bits of its bf16 elements.
+    m.def("_dbg_mxfp4_group_exponent", [](py::buffer bf16_bits) {
+        py::buffer_info in = bf16_bits.request();
+        if (in.itemsize != 2)
+            throw std::invalid_argument(
+                "_dbg_mxfp4_group_exponent takes the uint16 bits of a bf16 group");
+        const uint16_t* h = static_cast<const uint16_t*>(in.ptr);
+        uint32_t key = 0;
+        for (py::ssize_t i = 0; i < in.size; i++) key = mxfp4::key_step(key, h[i]);
+        return static_cast<int>(mxfp4::group_exponent(key));
+    });
+    // One e2m1 code per byte (not packed) for each bf16 under scale byte E.
+    m.def("_dbg_mxfp4_encode", [](py::buffer bf16_bits, int E) {
+        py::buffer_info in = bf16_bits.request();
+        if (in.itemsize != 2)
+            throw std::invalid_argument("_dbg_mxfp4_encode takes a uint16 buffer");
+        if (E < 0 || E > 255) throw std::invalid_argument("_dbg_mxfp4_encode: E is a byte");
+        const uint16_t* h = static_cast<const uint16_t*>(in.ptr);
+        std::string out(static_cast<size_t>(in.size), '\0');
+        for (size_t i = 0; i < out.size(); i++)
+            out[i] = static_cast<char>(mxfp4::encode(h[i], static_cast<uint8_t>(E)));
+        return py::bytes(out);
+    });
+    // bf16 bits (as bytes) for each code (one per byte) under scale byte E.
+    m.def("_dbg_mxfp4_decode", [](py::buffer codes, int E) {
+        py::buffer_info in = codes.request();
+        if (in.itemsize != 1)
+            throw std::invalid_argument("_dbg_mxfp4_decode takes a uint8 buffer");
+        if (E < 0 || E > 255) throw std::invalid_argument("_dbg_mxfp4_decode: E is a byte");
+        const uint8_t* c = static_cast<const uint8_t*>(in.ptr);
+        std::vector<uint16_t> out(static_cast<size_t>(in.size));
+        for (size_t i = 0; i < out.size(); i++)
+            out[i] = mxfp4::decode(c[i], static_cast<uint8_t>(E));
+        return py::bytes(reinterpret_cast<const char*>(out.data()), out.size() * 2);
     });
 
     // ---- debug/test surface (wire format + mempool) ----

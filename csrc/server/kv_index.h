@@ -45,6 +45,10 @@
 
 namespace ifs {
 
+// What a stored block holds. The values are the snapshot file's codec word
+// (0 and 1 predate mxfp4), so they never change.
+enum class PageCodec : uint8_t { kNone = 0, kFp8 = 1, kMxfp4 = 2 };
+
 // One stored block. Refcounted: the kv map holds one ref; in-flight reads
 // hold another so purge cannot free memory under an active copy.
 // Slab-allocated: prefill writes create thousands of entries per request,
@@ -55,9 +59,10 @@ struct BlockEntry : RefCounted {
     int pool_idx = -1;
     Shard* shard = nullptr;
     bool committed = false;
-    // fp8-compressed page (extension): `size` is the STORED byte size
-    // (half the logical bf16 page); reads dequantize with `scale`.
-    bool fp8 = false;
+    // Compressed page (extension): `size` is the STORED byte size. fp8:
+    // half the logical bf16 page, reads dequantize with `scale`. mxfp4:
+    // 17/64 of it, the scales are inside the block and `scale` is unused.
+    PageCodec codec = PageCodec::kNone;
     float scale = 1.f;
     uint32_t born_sec = 0;  // CLOCK_MONOTONIC seconds at insert (TTL)
     std::atomic<uint64_t> last_access{0};  // LRU tick (auto_evict)

@@ -753,15 +753,23 @@ void Server::op_local_write(Conn* c, const LocalView& msg, const ReqCtx& ctx) {
     // fp8 ingest compression (extension): bf16 pages stored at half size
     // with one scale per page; requires a 16-byte-divisible page.
     const bool quant = (msg.flags & kLocalFlagQuantFp8) != 0;
+    // mxfp4 ingest compression (extension): bf16 pages stored as e2m1 codes
+    // (page/4 bytes) followed by one e8m0 scale byte per 32 elements
+    // (page/64 bytes); requires whole 32-element groups.
+    const bool mx = (msg.flags & kLocalFlagQuantMxfp4) != 0;
+    if (quant && mx) return reply_local(c, ctx, INVALID_REQ);
     if (quant && (page % 16 != 0)) return reply_local(c, ctx, INVALID_REQ);
-    // The quantize kernel loads 16 bytes per lane: every source page must
+    if (mx && (page % 64 != 0)) return reply_local(c, ctx, INVALID_REQ);
+    // The quantize kernels load 16 bytes per lane: every source page must
     // start 16-byte aligned (pool blocks always do).
-    if (quant) {
+    if (quant || mx) {
         for (size_t i = 0; i < nb; i++)
             if (reinterpret_cast<uintptr_t>(client_ptr + msg.blocks[i].second) % 16 != 0)
                 return reply_local(c, ctx, INVALID_REQ);
     }
-    const size_t stored = quant ? page / 2 : page;
+    const size_t stored = quant ? page / 2 : mx ? page / 4 + page / 64 : page;
+    const PageCodec codec =
+        quant ? PageCodec::kFp8 : mx ? PageCodec::kMxfp4 : PageCodec::kNone;
 
     // Phase A — dedup check only (shared stripe locks, prefetch-pipelined).
     // The authoritative first-write-wins decision happens at the insert pass
@@ -830,6 +838,8 @@ void Server::op_local_write(Conn* c, const LocalView& msg, const ReqCtx& ctx) {
     if (quant) {
         job.xform = Shard::CopyJob::Xform::kQuantBf16Fp8;
         job.scales_out = scales_out;
+    } else if (mx) {
+        job.xform = Shard::CopyJob::Xform::kQuantBf16Mxfp4;
     }
     for (size_t i = 0; i < n_fresh; i++) {
         auto* e = slab_batch.make();
@@ -838,7 +848,7 @@ void Server::op_local_write(Conn* c, const LocalView& msg, const ReqCtx& ctx) {
         e->pool_idx = slots[i].second;
         e->shard = shard;
         e->committed = false;
-        e->fp8 = quant;
+        e->codec = codec;
         e->born_sec = KvIndex::now_sec();
         e->last_access.store(t, std::memory_order_relaxed);
         entries->emplace_back(e);
@@ -968,7 +978,8 @@ void Server::op_local_read(Conn* c, const LocalView& msg, const ReqCtx& ctx) {
     // traffic through one GPU's remote-read path and its own CUs.
     // IFS_CROSS_COPY=reader flips to pull for topologies where the owner
     // GPUs are compute-saturated; it requires a shard on the reader's GPU.
-    // fp8-compressed entries go into separate dequantizing jobs.
+    // fp8- and mxfp4-compressed entries go into separate dequantizing jobs,
+    // one group per codec, so one read may mix plain, fp8 and mxfp4 keys.
     static const bool cross_pull = [] {
         const char* v = getenv("IFS_CROSS_COPY");
         return v && std::string(v) == "reader";
@@ -983,6 +994,7 @@ void Server::op_local_read(Conn* c, const LocalView& msg, const ReqCtx& ctx) {
     };
     std::map<Shard*, Shard::CopyJob> jobs;
     std::map<Shard*, Shard::CopyJob> qjobs;
+    std::map<Shard*, Shard::CopyJob> mxjobs;
     auto held = std::make_shared<std::vector<Ref<BlockEntry>>>();
     held->reserve(msg.blocks.size());
     uint64_t read_tick = index_.tick();
@@ -1001,16 +1013,22 @@ void Server::op_local_read(Conn* c, const LocalView& msg, const ReqCtx& ctx) {
             e->last_access.store(read_tick, std::memory_order_relaxed);
             // fp8 entries: the page must be the written size, and the
             // dequantize kernel stores 16 bytes per lane into the client.
-            if (e->fp8 && (e->size * 2 != page ||
-                           reinterpret_cast<uintptr_t>(client_ptr + b.second) % 16 != 0)) {
+            // mxfp4 entries likewise: stored = 17/64 of the page.
+            const bool fp8 = e->codec == PageCodec::kFp8;
+            const bool mx = e->codec == PageCodec::kMxfp4;
+            if ((fp8 && e->size * 2 != page) || (mx && e->size * 64 != page * 17) ||
+                ((fp8 || mx) &&
+                 reinterpret_cast<uintptr_t>(client_ptr + b.second) % 16 != 0)) {
                 err = INVALID_REQ;
                 return false;
             }
-            auto& job = (e->fp8 ? qjobs : jobs)[exec_shard(e->shard)];
+            auto& job = (fp8 ? qjobs : mx ? mxjobs : jobs)[exec_shard(e->shard)];
             job.bytes_per_block = page;
-            if (e->fp8) {
+            if (fp8) {
                 job.xform = Shard::CopyJob::Xform::kDequantFp8Bf16;
                 job.scales_in.push_back(e->scale);
+            } else if (mx) {
+                job.xform = Shard::CopyJob::Xform::kDequantMxfp4Bf16;
             }
             job.src.push_back(reinterpret_cast<uint64_t>(e->ptr));
             job.dst.push_back(reinterpret_cast<uint64_t>(client_ptr + b.second));
@@ -1023,13 +1041,14 @@ void Server::op_local_read(Conn* c, const LocalView& msg, const ReqCtx& ctx) {
     n_reads_.fetch_add(1);
     bytes_out_.fetch_add(msg.blocks.size() * page);
     bool sync_resp = (msg.flags & kLocalFlagSyncResponse) != 0;
-    if (jobs.empty() && qjobs.empty())
+    if (jobs.empty() && qjobs.empty() && mxjobs.empty())
         return reply_local(c, ctx, sync_resp ? FINISH : TASK_ACCEPTED);
 
     c->remain.fetch_add(1);
     c->ref();
     auto pending =
-        std::make_shared<std::atomic<int>>(static_cast<int>(jobs.size() + qjobs.size()));
+        std::make_shared<std::atomic<int>>(
+            static_cast<int>(jobs.size() + qjobs.size() + mxjobs.size()));
     auto all_ok = std::make_shared<std::atomic<bool>>(true);
     auto submit_one = [&](Shard* shard, Shard::CopyJob& job) -> bool {
         Shard::CopyJob j = std::move(job);
@@ -1067,6 +1086,8 @@ void Server::op_local_read(Conn* c, const LocalView& msg, const ReqCtx& ctx) {
     for (auto& [shard, job] : jobs)
         if (!submit_one(shard, job)) return;
     for (auto& [shard, job] : qjobs)
+        if (!submit_one(shard, job)) return;
+    for (auto& [shard, job] : mxjobs)
         if (!submit_one(shard, job)) return;
     if (dbg && msg.blocks.size() > 256)
         fprintf(stderr, "[rdbg] read n=%zu collect=%.0f submit=%.0f\n", msg.blocks.size(),
@@ -1450,9 +1471,9 @@ bool Server::collect_read_entries(const std::vector<std::string>& keys,
     return index_.for_each_batched<KvIndex::Lock::kShared>(
         keys.size(), hashes.data(), 0, [&](KvMap& m, size_t i) {
             Ref<BlockEntry>* v = index_.find_live(m, keys[i], hashes[i]);
-            // fp8-compressed entries are a local-GPU-path feature: the
-            // TCP/verbs fabric moves raw bytes and cannot dequantize.
-            if (!v || !(*v)->committed || (*v)->fp8) return false;
+            // Compressed (fp8, mxfp4) entries are a local-GPU-path feature:
+            // the TCP/verbs fabric moves raw bytes and cannot dequantize.
+            if (!v || !(*v)->committed || (*v)->codec != PageCodec::kNone) return false;
             (*v)->last_access.store(t, std::memory_order_relaxed);
             (*out)[i] = *v;
             return true;
@@ -1805,7 +1826,7 @@ namespace {
 constexpr uint64_t kSnapMagic = 0x53494653504e3150ull;  // "SIFSPN1P"
 struct SnapEntryHdr {
     uint32_t key_len;
-    uint32_t fp8;
+    uint32_t fp8;   // PageCodec: 0 plain, 1 fp8, 2 mxfp4 (the name predates 2)
     uint64_t size;  // stored bytes
     float scale;
     uint32_t _pad;
@@ -1833,8 +1854,8 @@ bool Server::snapshot(const std::string& path, std::pair<size_t, size_t>* out) {
     for (auto& [key, ref] : pinned) {
         if (!ok) break;
         BlockEntry* e = ref.get();
-        SnapEntryHdr h{static_cast<uint32_t>(key.size()), e->fp8 ? 1u : 0u, e->size,
-                       e->scale, 0};
+        SnapEntryHdr h{static_cast<uint32_t>(key.size()), static_cast<uint32_t>(e->codec),
+                       e->size, e->scale, 0};
         buf.resize(e->size);
         if (e->shard->on_gpu()) {
             if (!gpu::memcpy_d2h(buf.data(), e->ptr, e->size)) {
@@ -1872,7 +1893,8 @@ bool Server::restore(const std::string& path, std::pair<size_t, size_t>* out) {
     bool ok = true;
     for (uint64_t i = 0; i < count && ok; i++) {
         SnapEntryHdr h{};
-        if (fread(&h, sizeof(h), 1, f) != 1 || h.key_len > 4096 || h.size > (1u << 30)) {
+        if (fread(&h, sizeof(h), 1, f) != 1 || h.key_len > 4096 || h.size > (1u << 30) ||
+            h.fp8 > static_cast<uint32_t>(PageCodec::kMxfp4)) {
             ok = false;
             break;
         }
@@ -1905,7 +1927,7 @@ bool Server::restore(const std::string& path, std::pair<size_t, size_t>* out) {
         e->size = h.size;
         e->pool_idx = pool_idx;
         e->shard = shard;
-        e->fp8 = h.fp8 != 0;
+        e->codec = static_cast<PageCodec>(h.fp8);
         e->scale = h.scale;
         e->born_sec = KvIndex::now_sec();
         e->committed = true;

@@ -272,7 +272,8 @@ bool Shard::submit_copy(CopyJob&& job) {
         for (size_t i = 0; i < n && aligned; i++)
             aligned = (job.src[i] % 16 == 0) && (job.dst[i] % 16 == 0);
     }
-    // The fp8 kernels have no byte fallback: they only ever run aligned.
+    // The fp8 and mxfp4 kernels have no byte fallback: they only ever run
+    // aligned.
     if (!aligned && job.xform != CopyJob::Xform::kCopy) return false;
 
     // HIP stream enqueues are thread-safe; each job's ops precede its event
@@ -353,11 +354,21 @@ bool Shard::submit_copy(CopyJob&& job) {
             ok = ok && gpu::launch_quant_blocks(opt_.device, sc.stream, dsrc, ddst,
                                                 slot->h_scale, static_cast<int>(take),
                                                 job.bytes_per_block / 2);
-        } else {  // kDequantFp8Bf16 (kernel reads desc + scale once per WG)
+        } else if (job.xform == CopyJob::Xform::kDequantFp8Bf16) {
+            // (kernel reads desc + scale once per WG)
             memcpy(slot->h_scale, job.scales_in.data() + off, take * sizeof(float));
             ok = ok && gpu::launch_dequant_blocks(opt_.device, sc.stream, dsrc, ddst,
                                                   slot->h_scale, static_cast<int>(take),
                                                   job.bytes_per_block / 2);
+        } else if (job.xform == CopyJob::Xform::kQuantBf16Mxfp4) {
+            // Scales live inside the stored block: h_scale is not used.
+            ok = ok && gpu::launch_quant_blocks_mxfp4(opt_.device, sc.stream, dsrc, ddst,
+                                                      static_cast<int>(take),
+                                                      job.bytes_per_block / 2);
+        } else {  // kDequantMxfp4Bf16
+            ok = ok && gpu::launch_dequant_blocks_mxfp4(opt_.device, sc.stream, dsrc, ddst,
+                                                        static_cast<int>(take),
+                                                        job.bytes_per_block / 2);
         }
         ok = ok && gpu::event_record(slot->event, sc.stream);
         if (!ok) {

@@ -45,8 +45,15 @@ class Shard {
     struct CopyJob {
         // kCopy moves bytes; the fp8 transforms convert while moving
         // (bytes_per_block is the LOGICAL bf16 size in all modes — the fp8
-        // side of a transform is half that).
-        enum class Xform { kCopy = 0, kQuantBf16Fp8, kDequantFp8Bf16 };
+        // side of a transform is half that, the mxfp4 side 17/64 of it with
+        // its scales inside the block: no scales_out / scales_in).
+        enum class Xform {
+            kCopy = 0,
+            kQuantBf16Fp8,
+            kDequantFp8Bf16,
+            kQuantBf16Mxfp4,
+            kDequantMxfp4Bf16
+        };
         std::vector<uint64_t> src;
         std::vector<uint64_t> dst;
         size_t bytes_per_block = 0;

@@ -48,8 +48,8 @@ def parse_args():
                         "--size is derived from --seq-len x --batch")
     p.add_argument("--seq-len", type=int, default=8192)
     p.add_argument("--batch", type=int, default=1)
-    p.add_argument("--quant", choices=["fp8"], default=None,
-                   help="store pages fp8-compressed (local-GPU path, bf16)")
+    p.add_argument("--quant", choices=["fp8", "mxfp4"], default=None,
+                   help="store pages fp8- or mxfp4-compressed (local-GPU path, bf16)")
     p.add_argument("--verify", action="store_true")
     p.add_argument("--json", action="store_true", help="print a JSON summary")
     p.add_argument("--spawn-server", action="store_true",

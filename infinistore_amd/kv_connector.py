@@ -52,7 +52,9 @@ class PagedKVConnector:
     def __init__(self, host: str, port: int, model_tag: str, n_layers: int,
                  local: bool = True, quant: Optional[str] = None):
         """quant="fp8": store KV pages fp8-compressed (half HBM per page,
-        ~3-bit mantissa; reads return bf16). Local path + bf16 KV only."""
+        ~3-bit mantissa; reads return bf16). quant="mxfp4": OCP MXFP4 pages
+        (17/32 byte per element, one power-of-two scale per 32 elements;
+        page size a multiple of 32 elements). Local path + bf16 KV only."""
         self.model_tag = model_tag
         self.n_layers = n_layers
         self.quant = quant

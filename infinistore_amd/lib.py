@@ -360,6 +360,7 @@ class InfinityConnection:
         return "\0".join(keys).encode()
 
     FLAG_QUANT_FP8 = 2  # wire flag: store bf16 pages fp8-compressed
+    FLAG_QUANT_MXFP4 = 4  # wire flag: store bf16 pages as OCP MXFP4
 
     def write_pages(self, cache: torch.Tensor, keys, offsets, page_size: int,
                     sync: bool = False, quant: Optional[str] = None):
@@ -371,11 +372,31 @@ class InfinityConnection:
         scale per page) at HALF the HBM footprint; requires a bf16 cache
         tensor, and reads of these keys dequantize back to bf16
         transparently. Doubles effective cache capacity at ~3-bit mantissa
-        precision — the usual KV-cache quantization trade."""
+        precision — the usual KV-cache quantization trade.
+
+        quant="mxfp4": store the pages as OCP microscaling FP4 — e2m1
+        elements {0, .5, 1, 1.5, 2, 3, 4, 6} with one power-of-two (e8m0)
+        scale per 32 consecutive elements, kept inside the stored block. A
+        page takes 17/32 of a byte per element: 3.76x smaller than bf16 and
+        1.88x smaller than quant="fp8". Requires a bf16 cache,
+        page_size % 32 == 0, a 16-byte-aligned cache and page offsets that
+        are multiples of 8 elements (ValueError otherwise, before anything
+        is sent). Reads dequantize transparently and must use the written
+        page_size. Values round to nearest (ties to even) after scaling by
+        the group's absmax exponent; +-inf and anything above the group's
+        range saturate to +-6 x scale; a group holding a NaN reads back as
+        all NaN (e2m1 has no NaN code, so the OCP convention marks the
+        group's scale); -0 keeps its sign."""
         self._verify(cache)
         assert self.local_connected, "write_pages uses the local GPU path"
         flags = 0
-        if quant is not None:
+        if quant == "mxfp4":
+            if cache.dtype != torch.bfloat16:
+                raise ValueError("mxfp4 quant requires a bf16 cache")
+            if page_size <= 0 or page_size % 32 != 0:
+                raise ValueError("mxfp4 quant needs page_size % 32 == 0")
+            flags = self.FLAG_QUANT_MXFP4
+        elif quant is not None:
             assert quant == "fp8", f"unsupported quant mode {quant!r}"
             assert cache.dtype == torch.bfloat16, "fp8 quant requires a bf16 cache"
             assert page_size % 8 == 0, "fp8 quant needs page_size % 8 == 0"
@@ -386,7 +407,7 @@ class InfinityConnection:
             # the quantize kernel loads 16 bytes (8 bf16) per lane
             if cache.data_ptr() % 16 != 0 or (offs % np.uint64(8)).any():
                 raise ValueError(
-                    "fp8 quant needs a 16-byte-aligned cache and page offsets "
+                    f"{quant} quant needs a 16-byte-aligned cache and page offsets "
                     "that are multiples of 8 elements")
         if isinstance(keys, (bytes, bytearray, memoryview)):
             ret = self.conn.rw_local_blob(

@@ -54,7 +54,8 @@ class InfiniStoreKVAdapter:
         page_elems: elements per page per layer (``2*block_tokens*n_kv*hd``
             for the usual K+V layout).
         local: same-host GPU path (IPC + HIP gather) vs the fabric path.
-        quant: "fp8" to store pages compressed (bf16 engines only).
+        quant: "fp8" or "mxfp4" to store pages compressed (bf16 engines
+            only; "mxfp4" needs page_elems % 32 == 0).
     """
 
     def __init__(self, host: str, port: int, model_tag: str, n_layers: int,
