@@ -1,0 +1,88 @@
+// Page codecs: the formats a stored block can have, one table row each.
+//
+// Everything that defines a format outside its kernels is here: the wire
+// flag that asks for it, which logical page sizes it takes, how many bytes
+// the stored block has, and whether a per-page scale travels next to the
+// block. Server, shard, launcher, bindings and the Python client all derive
+// their size and alignment rules from this table (docs/design.md, "page
+// codecs"). Host-only: no HIP includes.
+#pragma once
+
+#include <cstddef>
+#include <cstdint>
+
+#include "protocol.h"
+
+namespace ifs {
+
+// What a stored block holds. The values are the snapshot file's codec word
+// (0 and 1 predate mxfp4), so they never change.
+enum class PageCodec : uint8_t { kNone = 0, kFp8 = 1, kMxfp4 = 2 };
+
+// Which way a transform runs: kStore converts a logical page into its stored
+// block (write path), kLoad converts a stored block back (read path).
+enum class PageDir : uint8_t { kStore, kLoad };
+
+// The compressed codecs take bf16 pages.
+constexpr size_t kPageElemBytes = 2;
+
+struct PageCodecInfo {
+    const char* name;
+    uint32_t flag;           // PackedLocalHdr.flags bit that requests it
+    uint32_t page_multiple;  // logical page bytes are a multiple of this
+    uint32_t num, den;       // stored bytes = page * num / den, exactly
+    bool page_scale;         // one fp32 scale per page in BlockEntry::scale
+};
+
+// Indexed by PageCodec. fp8: one byte per bf16 element (page / 2), 16 bytes
+// per lane. mxfp4: e2m1 codes (page / 4) plus one e8m0 scale byte per 32
+// elements (page / 64), whole 32-element groups only.
+constexpr PageCodecInfo kPageCodecs[] = {
+    {"none", 0, 1, 1, 1, false},
+    {"fp8", kLocalFlagQuantFp8, 16, 1, 2, true},
+    {"mxfp4", kLocalFlagQuantMxfp4, 64, 17, 64, false},
+};
+constexpr size_t kNumPageCodecs = sizeof(kPageCodecs) / sizeof(kPageCodecs[0]);
+static_assert(kPageCodecs[1].page_multiple % kPageCodecs[1].den == 0 &&
+                  kPageCodecs[2].page_multiple % kPageCodecs[2].den == 0,
+              "a legal page divides exactly into its stored size");
+
+inline bool page_codec_known(uint32_t id) { return id < kNumPageCodecs; }
+
+inline const PageCodecInfo& page_codec_info(PageCodec c) {
+    return kPageCodecs[static_cast<size_t>(c)];
+}
+
+// Codec a request's flags ask for; false when more than one quant flag is set.
+inline bool page_codec_from_flags(uint32_t flags, PageCodec* out) {
+    *out = PageCodec::kNone;
+    for (size_t i = 1; i < kNumPageCodecs; i++) {
+        if (!(flags & kPageCodecs[i].flag)) continue;
+        if (*out != PageCodec::kNone) return false;
+        *out = static_cast<PageCodec>(i);
+    }
+    return true;
+}
+
+// Codecs other than kNone convert while moving. Their kernels move 16 bytes
+// per lane and have no byte fallback: every page address, logical or stored,
+// must be 16-byte aligned.
+inline bool page_codec_transforms(PageCodec c) { return c != PageCodec::kNone; }
+
+inline bool page_legal(PageCodec c, size_t page) {
+    return page % page_codec_info(c).page_multiple == 0;
+}
+
+// Stored bytes of a legal page.
+inline size_t stored_bytes(PageCodec c, size_t page) {
+    const PageCodecInfo& i = page_codec_info(c);
+    return page / i.den * i.num;
+}
+
+// Read side: does a block of `stored` bytes hold a logical page of `page`?
+inline bool stored_matches(PageCodec c, size_t stored, size_t page) {
+    const PageCodecInfo& i = page_codec_info(c);
+    return stored * i.den == page * i.num;
+}
+
+}  // namespace ifs

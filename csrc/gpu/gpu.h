@@ -15,6 +15,8 @@
 #include <cstdint>
 #include <string>
 
+#include "../core/page_codec.h"
+
 namespace ifs {
 namespace gpu {
 
@@ -98,34 +100,23 @@ bool launch_copy_blocks(int dev, Stream s, const uint64_t* dev_src_ptrs,
 bool launch_copy_blocks_inline(int dev, Stream s, const uint64_t* src_ptrs,
                                const uint64_t* dst_ptrs, int n_blocks, size_t bytes_per_block);
 
-// --- fp8 KV compression ------------------------------------------------------
-// Quantize n blocks of bf16 (elems_per_block each) into fp8 e4m3fn blocks of
-// half the byte size; one scale (finite absmax/448) per block ->
-// dev_scales[i]. The codec itself is fp8_codec.h. Both kernels move 16 bytes
-// per lane: elems_per_block % 8 == 0 (checked here) and every block pointer
-// 16-byte aligned (the CALLER checks: the descriptors may be device memory).
-bool launch_quant_blocks(int dev, Stream s, const uint64_t* dev_src_ptrs,
-                         const uint64_t* dev_dst_ptrs, float* dev_scales, int n_blocks,
-                         size_t elems_per_block);
-// Inverse: fp8 blocks + scales -> bf16 blocks.
-bool launch_dequant_blocks(int dev, Stream s, const uint64_t* dev_src_ptrs,
-                           const uint64_t* dev_dst_ptrs, const float* dev_scales, int n_blocks,
-                           size_t elems_per_block);
-
-// --- mxfp4 KV compression ----------------------------------------------------
-// Quantize n blocks of bf16 (elems_per_block each) into OCP MXFP4 blocks of
-// elems/2 + elems/32 bytes: e2m1 codes, two per byte, then one e8m0 scale
-// byte per 32 elements. The scales live inside the block, so there is no
-// scale array. The codec itself is mxfp4_codec.h. elems_per_block % 32 == 0
-// (checked here); every block pointer 16-byte aligned (the CALLER checks:
-// the descriptors may be device memory).
-bool launch_quant_blocks_mxfp4(int dev, Stream s, const uint64_t* dev_src_ptrs,
-                               const uint64_t* dev_dst_ptrs, int n_blocks,
-                               size_t elems_per_block);
-// Inverse: mxfp4 blocks -> bf16 blocks.
-bool launch_dequant_blocks_mxfp4(int dev, Stream s, const uint64_t* dev_src_ptrs,
-                                 const uint64_t* dev_dst_ptrs, int n_blocks,
-                                 size_t elems_per_block);
+// --- KV page compression -----------------------------------------------------
+// Convert n blocks of bf16 (elems_per_block each) into stored blocks of
+// `codec` (kStore), or stored blocks back into bf16 (kLoad). Sizes per codec:
+// core/page_codec.h. Every block pointer is 16-byte aligned (the CALLER
+// checks: the descriptors may be device memory). kNone is refused: plain
+// pages go through launch_copy_blocks.
+//  * fp8 (fp8_codec.h): e4m3fn blocks of half the byte size and one scale
+//    (finite absmax/448) per block, written to dev_scales[i] by kStore and
+//    read from it by kLoad. Both kernels move 16 bytes per lane:
+//    elems_per_block % 8 == 0 (checked here).
+//  * mxfp4 (mxfp4_codec.h): OCP MXFP4 blocks of elems/2 + elems/32 bytes:
+//    e2m1 codes, two per byte, then one e8m0 scale byte per 32 elements. The
+//    scales live inside the block, so dev_scales is ignored.
+//    elems_per_block % 32 == 0 (checked here).
+bool launch_transform_blocks(int dev, Stream s, PageCodec codec, PageDir dir,
+                             const uint64_t* dev_src_ptrs, const uint64_t* dev_dst_ptrs,
+                             float* dev_scales, int n_blocks, size_t elems_per_block);
 // Groups of 32 elements that one workgroup of either mxfp4 kernel covers per
 // loop iteration (four lanes per group).
 constexpr int kMxfp4GroupsPerIter = 64;

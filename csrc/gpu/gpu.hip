@@ -258,18 +258,37 @@ bool event_query(Event e) {
 // per-unit desc[b] indexing either taxed PCIe at ~payload/64 (pinned) or
 // forced per-job uploads that rocclr ran as single-workgroup blits at
 // ~110 µs each (profiles/rocprof_bench_r02.txt).
+
+// The shared prologue of the 2D-mapped kernels (vector copy, byte copy, mxfp4
+// quantize and dequantize): lane 0 reads block b's descriptor pair, LDS
+// broadcasts it into sd[0] = src, sd[1] = dst; returns the workgroup's chunk.
+// chunk is written as blockIdx.x - b * chunks, not as `%`: with `%` the
+// compiler sinks the division into the lane-0 branch and divides twice (one
+// more SGPR in both copy kernels); this form compiles to the same
+// instructions as the prologue written out in each kernel.
+__device__ __forceinline__ uint32_t block_chunk_descs(const uint64_t* __restrict__ src_ptrs,
+                                                      const uint64_t* __restrict__ dst_ptrs,
+                                                      uint32_t chunks_per_block,
+                                                      uint64_t (&sd)[2]) {
+    uint32_t b = blockIdx.x / chunks_per_block;
+    uint32_t chunk = blockIdx.x - b * chunks_per_block;
+    __shared__ uint64_t lds[2];
+    if (threadIdx.x == 0) {
+        lds[0] = src_ptrs[b];
+        lds[1] = dst_ptrs[b];
+    }
+    __syncthreads();
+    sd[0] = lds[0];
+    sd[1] = lds[1];
+    return chunk;
+}
+
 __global__ void copy_blocks_vec_kernel(const uint64_t* __restrict__ src_ptrs,
                                        const uint64_t* __restrict__ dst_ptrs,
                                        uint32_t chunks_per_block,
                                        uint64_t units_per_block) {
-    uint32_t b = blockIdx.x / chunks_per_block;
-    uint32_t chunk = blockIdx.x % chunks_per_block;
-    __shared__ uint64_t sd[2];
-    if (threadIdx.x == 0) {
-        sd[0] = src_ptrs[b];
-        sd[1] = dst_ptrs[b];
-    }
-    __syncthreads();
+    uint64_t sd[2];
+    uint32_t chunk = block_chunk_descs(src_ptrs, dst_ptrs, chunks_per_block, sd);
     const uint4* s = reinterpret_cast<const uint4*>(sd[0]);
     uint4* d = reinterpret_cast<uint4*>(sd[1]);
     uint64_t stride = static_cast<uint64_t>(chunks_per_block) * blockDim.x;
@@ -324,14 +343,8 @@ __global__ void copy_blocks_byte_kernel(const uint64_t* __restrict__ src_ptrs,
                                         const uint64_t* __restrict__ dst_ptrs,
                                         uint32_t chunks_per_block,
                                         uint64_t bytes_per_block) {
-    uint32_t b = blockIdx.x / chunks_per_block;
-    uint32_t chunk = blockIdx.x % chunks_per_block;
-    __shared__ uint64_t sd[2];
-    if (threadIdx.x == 0) {
-        sd[0] = src_ptrs[b];
-        sd[1] = dst_ptrs[b];
-    }
-    __syncthreads();
+    uint64_t sd[2];
+    uint32_t chunk = block_chunk_descs(src_ptrs, dst_ptrs, chunks_per_block, sd);
     const uint8_t* s = reinterpret_cast<const uint8_t*>(sd[0]);
     uint8_t* d = reinterpret_cast<uint8_t*>(sd[1]);
     uint64_t stride = static_cast<uint64_t>(chunks_per_block) * blockDim.x;
@@ -455,32 +468,6 @@ __global__ void dequant_blocks_fp8_bf16_kernel(const uint64_t* __restrict__ src_
     }
 }
 
-bool launch_quant_blocks(int dev, Stream stream, const uint64_t* dev_src_ptrs,
-                         const uint64_t* dev_dst_ptrs, float* dev_scales, int n_blocks,
-                         size_t elems_per_block) {
-    if (n_blocks <= 0) return true;
-    if (elems_per_block % 8 != 0) return false;
-    HIP_OK(hipSetDevice(dev));
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(quant_blocks_bf16_fp8_kernel, dim3(n_blocks), dim3(512), 0, s,
-                       dev_src_ptrs, dev_dst_ptrs, dev_scales, elems_per_block);
-    HIP_OK(hipGetLastError());
-    return true;
-}
-
-bool launch_dequant_blocks(int dev, Stream stream, const uint64_t* dev_src_ptrs,
-                           const uint64_t* dev_dst_ptrs, const float* dev_scales, int n_blocks,
-                           size_t elems_per_block) {
-    if (n_blocks <= 0) return true;
-    if (elems_per_block % 8 != 0) return false;
-    HIP_OK(hipSetDevice(dev));
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(dequant_blocks_fp8_bf16_kernel, dim3(n_blocks), dim3(512), 0, s,
-                       dev_src_ptrs, dev_dst_ptrs, dev_scales, elems_per_block);
-    HIP_OK(hipGetLastError());
-    return true;
-}
-
 // --- mxfp4 KV-cache compression ---------------------------------------------
 // bf16 pages <-> OCP microscaling FP4: e2m1 codes, two per byte, followed by
 // one e8m0 scale byte per group of 32 elements (block layout and rules:
@@ -502,14 +489,8 @@ __global__ void quant_blocks_bf16_mxfp4_kernel(const uint64_t* __restrict__ src_
                                                const uint64_t* __restrict__ dst_ptrs,
                                                uint32_t chunks_per_block,
                                                uint64_t elems_per_block) {
-    uint32_t b = blockIdx.x / chunks_per_block;
-    uint32_t chunk = blockIdx.x % chunks_per_block;
-    __shared__ uint64_t sd[2];
-    if (threadIdx.x == 0) {
-        sd[0] = src_ptrs[b];
-        sd[1] = dst_ptrs[b];
-    }
-    __syncthreads();
+    uint64_t sd[2];
+    uint32_t chunk = block_chunk_descs(src_ptrs, dst_ptrs, chunks_per_block, sd);
     const uint4* src4 = reinterpret_cast<const uint4*>(sd[0]);
     uint32_t* codes = reinterpret_cast<uint32_t*>(sd[1]);
     uint8_t* scales = reinterpret_cast<uint8_t*>(sd[1]) + elems_per_block / 2;
@@ -538,14 +519,8 @@ __global__ void dequant_blocks_mxfp4_bf16_kernel(const uint64_t* __restrict__ sr
                                                  const uint64_t* __restrict__ dst_ptrs,
                                                  uint32_t chunks_per_block,
                                                  uint64_t elems_per_block) {
-    uint32_t b = blockIdx.x / chunks_per_block;
-    uint32_t chunk = blockIdx.x % chunks_per_block;
-    __shared__ uint64_t sd[2];
-    if (threadIdx.x == 0) {
-        sd[0] = src_ptrs[b];
-        sd[1] = dst_ptrs[b];
-    }
-    __syncthreads();
+    uint64_t sd[2];
+    uint32_t chunk = block_chunk_descs(src_ptrs, dst_ptrs, chunks_per_block, sd);
     const uint32_t* codes = reinterpret_cast<const uint32_t*>(sd[0]);
     const uint8_t* scales = reinterpret_cast<const uint8_t*>(sd[0]) + elems_per_block / 2;
     uint4* dst4 = reinterpret_cast<uint4*>(sd[1]);
@@ -563,38 +538,46 @@ __global__ void dequant_blocks_mxfp4_bf16_kernel(const uint64_t* __restrict__ sr
     }
 }
 
-static bool launch_mxfp4(bool quant, int dev, Stream stream, const uint64_t* dev_src_ptrs,
-                         const uint64_t* dev_dst_ptrs, int n_blocks, size_t elems_per_block) {
+// The one entry for every transforming codec (gpu.h). A new codec is a kernel
+// pair above and one case here.
+bool launch_transform_blocks(int dev, Stream stream, PageCodec codec, PageDir dir,
+                             const uint64_t* dev_src_ptrs, const uint64_t* dev_dst_ptrs,
+                             float* dev_scales, int n_blocks, size_t elems_per_block) {
     if (n_blocks <= 0) return true;
-    if (elems_per_block == 0 || elems_per_block % mxfp4::kGroupElems != 0) return false;
-    HIP_OK(hipSetDevice(dev));
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    uint32_t chunks = copy_chunks_per_block(elems_per_block / 8, n_blocks, kMxfp4Threads);
-    dim3 grid(static_cast<uint32_t>(n_blocks) * chunks);
-    if (quant)
-        hipLaunchKernelGGL(quant_blocks_bf16_mxfp4_kernel, grid, dim3(kMxfp4Threads), 0, s,
-                           dev_src_ptrs, dev_dst_ptrs, chunks,
-                           static_cast<uint64_t>(elems_per_block));
-    else
-        hipLaunchKernelGGL(dequant_blocks_mxfp4_bf16_kernel, grid, dim3(kMxfp4Threads), 0, s,
-                           dev_src_ptrs, dev_dst_ptrs, chunks,
-                           static_cast<uint64_t>(elems_per_block));
+    const bool store = dir == PageDir::kStore;
+    switch (codec) {
+        case PageCodec::kFp8:
+            if (elems_per_block % 8 != 0) return false;
+            HIP_OK(hipSetDevice(dev));
+            if (store)
+                hipLaunchKernelGGL(quant_blocks_bf16_fp8_kernel, dim3(n_blocks), dim3(512), 0, s,
+                                   dev_src_ptrs, dev_dst_ptrs, dev_scales, elems_per_block);
+            else
+                hipLaunchKernelGGL(dequant_blocks_fp8_bf16_kernel, dim3(n_blocks), dim3(512), 0,
+                                   s, dev_src_ptrs, dev_dst_ptrs, dev_scales, elems_per_block);
+            break;
+        case PageCodec::kMxfp4: {
+            if (elems_per_block == 0 || elems_per_block % mxfp4::kGroupElems != 0) return false;
+            HIP_OK(hipSetDevice(dev));
+            uint32_t chunks =
+                copy_chunks_per_block(elems_per_block / 8, n_blocks, kMxfp4Threads);
+            dim3 grid(static_cast<uint32_t>(n_blocks) * chunks);
+            if (store)
+                hipLaunchKernelGGL(quant_blocks_bf16_mxfp4_kernel, grid, dim3(kMxfp4Threads), 0,
+                                   s, dev_src_ptrs, dev_dst_ptrs, chunks,
+                                   static_cast<uint64_t>(elems_per_block));
+            else
+                hipLaunchKernelGGL(dequant_blocks_mxfp4_bf16_kernel, grid, dim3(kMxfp4Threads),
+                                   0, s, dev_src_ptrs, dev_dst_ptrs, chunks,
+                                   static_cast<uint64_t>(elems_per_block));
+            break;
+        }
+        default:
+            return false;
+    }
     HIP_OK(hipGetLastError());
     return true;
-}
-
-bool launch_quant_blocks_mxfp4(int dev, Stream stream, const uint64_t* dev_src_ptrs,
-                               const uint64_t* dev_dst_ptrs, int n_blocks,
-                               size_t elems_per_block) {
-    return launch_mxfp4(true, dev, stream, dev_src_ptrs, dev_dst_ptrs, n_blocks,
-                        elems_per_block);
-}
-
-bool launch_dequant_blocks_mxfp4(int dev, Stream stream, const uint64_t* dev_src_ptrs,
-                                 const uint64_t* dev_dst_ptrs, int n_blocks,
-                                 size_t elems_per_block) {
-    return launch_mxfp4(false, dev, stream, dev_src_ptrs, dev_dst_ptrs, n_blocks,
-                        elems_per_block);
 }
 
 // --- fingerprint -----------------------------------------------------------

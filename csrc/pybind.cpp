@@ -202,80 +202,56 @@ void copy_blocks_py(const std::vector<uint64_t>& src, const std::vector<uint64_t
         throw std::runtime_error(std::string("_dbg_copy_blocks failed: ") + gpu::last_error());
 }
 
-void require_quant_shape(const char* what, const std::vector<uint64_t>& src,
-                         const std::vector<uint64_t>& dst, size_t elems_per_block) {
+// The one body behind the four `_dbg_*quant*` kernel bindings: checks from the
+// codec table, then the production launcher. kStore returns the per-page
+// scales (empty for codecs that keep theirs inside the block); kLoad takes
+// them in `scales`.
+std::vector<float> transform_blocks_py(const char* what, PageCodec codec, PageDir dir,
+                                       const std::vector<uint64_t>& src,
+                                       const std::vector<uint64_t>& dst,
+                                       std::vector<float> scales, size_t elems_per_block,
+                                       int device) {
+    const PageCodecInfo& info = page_codec_info(codec);
+    const bool store = dir == PageDir::kStore;
     require_gpu_and_pairs(what, src, dst);
-    if (elems_per_block == 0 || elems_per_block % 8 != 0)
-        throw std::invalid_argument(std::string(what) + ": elems_per_block % 8 != 0");
+    if (elems_per_block == 0 || !page_legal(codec, elems_per_block * kPageElemBytes))
+        throw std::invalid_argument(std::string(what) + ": elems_per_block % " +
+                                    std::to_string(info.page_multiple / kPageElemBytes) +
+                                    " != 0");
     if (!all_aligned16(src, dst))
         throw std::invalid_argument(std::string(what) + ": pointers must be 16-byte aligned");
-}
-
-std::vector<float> quant_blocks_py(const std::vector<uint64_t>& src,
-                                   const std::vector<uint64_t>& dst, size_t elems_per_block,
-                                   int device) {
-    require_quant_shape("_dbg_quant_blocks", src, dst, elems_per_block);
     size_t n = src.size();
-    std::vector<float> scales(n);
+    if (info.page_scale && !store && scales.size() != n)
+        throw std::invalid_argument(std::string(what) + ": one scale per block");
+    scales.resize(info.page_scale ? n : 0);
     if (n == 0) return scales;
     Pinned<uint64_t> h_src(n), h_dst(n);
     Pinned<float> h_scale(n);
     memcpy(h_src.p, src.data(), n * 8);
     memcpy(h_dst.p, dst.data(), n * 8);
+    memcpy(h_scale.p, scales.data(), scales.size() * sizeof(float));
     ScopedStream st(device);
-    bool ok = gpu::launch_quant_blocks(device, st.s, h_src.p, h_dst.p, h_scale.p,
-                                       static_cast<int>(n), elems_per_block);
-    bool synced = gpu::stream_sync(st.s);
-    if (!ok || !synced)
-        throw std::runtime_error(std::string("_dbg_quant_blocks failed: ") + gpu::last_error());
-    memcpy(scales.data(), h_scale.p, n * sizeof(float));
-    return scales;
-}
-
-void dequant_blocks_py(const std::vector<uint64_t>& src, const std::vector<uint64_t>& dst,
-                       const std::vector<float>& scales, size_t elems_per_block, int device) {
-    require_quant_shape("_dbg_dequant_blocks", src, dst, elems_per_block);
-    if (scales.size() != src.size())
-        throw std::invalid_argument("_dbg_dequant_blocks: one scale per block");
-    size_t n = src.size();
-    if (n == 0) return;
-    Pinned<uint64_t> h_src(n), h_dst(n);
-    Pinned<float> h_scale(n);
-    memcpy(h_src.p, src.data(), n * 8);
-    memcpy(h_dst.p, dst.data(), n * 8);
-    memcpy(h_scale.p, scales.data(), n * sizeof(float));
-    ScopedStream st(device);
-    bool ok = gpu::launch_dequant_blocks(device, st.s, h_src.p, h_dst.p, h_scale.p,
-                                         static_cast<int>(n), elems_per_block);
-    bool synced = gpu::stream_sync(st.s);
-    if (!ok || !synced)
-        throw std::runtime_error(std::string("_dbg_dequant_blocks failed: ") +
-                                 gpu::last_error());
-}
-
-// mxfp4: the scales live inside the stored block, so both directions take
-// pointer lists only.
-void mxfp4_blocks_py(bool quant, const std::vector<uint64_t>& src,
-                     const std::vector<uint64_t>& dst, size_t elems_per_block, int device) {
-    const char* what = quant ? "_dbg_mxfp4_quant_blocks" : "_dbg_mxfp4_dequant_blocks";
-    require_gpu_and_pairs(what, src, dst);
-    if (elems_per_block == 0 || elems_per_block % mxfp4::kGroupElems != 0)
-        throw std::invalid_argument(std::string(what) + ": elems_per_block % 32 != 0");
-    if (!all_aligned16(src, dst))
-        throw std::invalid_argument(std::string(what) + ": pointers must be 16-byte aligned");
-    size_t n = src.size();
-    if (n == 0) return;
-    Pinned<uint64_t> h_src(n), h_dst(n);
-    memcpy(h_src.p, src.data(), n * 8);
-    memcpy(h_dst.p, dst.data(), n * 8);
-    ScopedStream st(device);
-    bool ok = quant ? gpu::launch_quant_blocks_mxfp4(device, st.s, h_src.p, h_dst.p,
-                                                     static_cast<int>(n), elems_per_block)
-                    : gpu::launch_dequant_blocks_mxfp4(device, st.s, h_src.p, h_dst.p,
-                                                       static_cast<int>(n), elems_per_block);
+    bool ok = gpu::launch_transform_blocks(device, st.s, codec, dir, h_src.p, h_dst.p,
+                                           h_scale.p, static_cast<int>(n), elems_per_block);
     bool synced = gpu::stream_sync(st.s);
     if (!ok || !synced)
         throw std::runtime_error(std::string(what) + " failed: " + gpu::last_error());
+    memcpy(scales.data(), h_scale.p, scales.size() * sizeof(float));
+    return scales;
+}
+
+// (codec id, stored bytes) of a request with these flags and this logical
+// page size, by the codec table alone (host-only).
+std::pair<int, size_t> page_codec_py(uint32_t flags, size_t page_bytes) {
+    PageCodec codec;
+    if (!page_codec_from_flags(flags, &codec))
+        throw std::invalid_argument("_dbg_page_codec: more than one quant flag");
+    if (!page_legal(codec, page_bytes))
+        throw std::invalid_argument(std::string("_dbg_page_codec: ") +
+                                    page_codec_info(codec).name + " pages are multiples of " +
+                                    std::to_string(page_codec_info(codec).page_multiple) +
+                                    " bytes");
+    return {static_cast<int>(codec), stored_bytes(codec, page_bytes)};
 }
 
 }  // namespace
@@ -567,12 +543,34 @@ PYBIND11_MODULE(_native, m) {
     m.def("_dbg_copy_blocks", &copy_blocks_py, py::arg("src_ptrs"), py::arg("dst_ptrs"),
           py::arg("bytes_per_block"), py::arg("device"), py::arg("path"),
           py::call_guard<py::gil_scoped_release>());
-    m.def("_dbg_quant_blocks", &quant_blocks_py, py::arg("src_ptrs"), py::arg("dst_ptrs"),
+    m.def("_dbg_quant_blocks",
+          [](const std::vector<uint64_t>& src, const std::vector<uint64_t>& dst,
+             size_t elems_per_block, int device) {
+              return transform_blocks_py("_dbg_quant_blocks", PageCodec::kFp8, PageDir::kStore,
+                                         src, dst, {}, elems_per_block, device);
+          },
+          py::arg("src_ptrs"), py::arg("dst_ptrs"), py::arg("elems_per_block"),
+          py::arg("device"), py::call_guard<py::gil_scoped_release>());
+    m.def("_dbg_dequant_blocks",
+          [](const std::vector<uint64_t>& src, const std::vector<uint64_t>& dst,
+             const std::vector<float>& scales, size_t elems_per_block, int device) {
+              transform_blocks_py("_dbg_dequant_blocks", PageCodec::kFp8, PageDir::kLoad, src,
+                                  dst, scales, elems_per_block, device);
+          },
+          py::arg("src_ptrs"), py::arg("dst_ptrs"), py::arg("scales"),
           py::arg("elems_per_block"), py::arg("device"),
           py::call_guard<py::gil_scoped_release>());
-    m.def("_dbg_dequant_blocks", &dequant_blocks_py, py::arg("src_ptrs"), py::arg("dst_ptrs"),
-          py::arg("scales"), py::arg("elems_per_block"), py::arg("device"),
-          py::call_guard<py::gil_scoped_release>());
+
+    // ---- debug/test surface (the codec table: csrc/core/page_codec.h) ----
+    m.def("_dbg_page_codec", &page_codec_py, py::arg("flags"), py::arg("page_bytes"));
+    // One (name, wire flag, page-size multiple in bf16 elements) per codec.
+    m.def("_page_codec_rows", [] {
+        std::vector<std::tuple<std::string, uint32_t, size_t>> rows;
+        for (const PageCodecInfo& i : kPageCodecs)
+            rows.emplace_back(i.name, i.flag,
+                              (i.page_multiple + kPageElemBytes - 1) / kPageElemBytes);
+        return rows;
+    });
 
     // ---- debug/test surface (fp8 codec on the host: csrc/gpu/fp8_codec.h) ----
     m.def("_dbg_fp8_encode", [](py::buffer f32) {
@@ -608,14 +606,16 @@ PYBIND11_MODULE(_native, m) {
     m.def("_dbg_mxfp4_quant_blocks",
           [](const std::vector<uint64_t>& src, const std::vector<uint64_t>& dst,
              size_t elems_per_block, int device) {
-              mxfp4_blocks_py(true, src, dst, elems_per_block, device);
+              transform_blocks_py("_dbg_mxfp4_quant_blocks", PageCodec::kMxfp4, PageDir::kStore,
+                                  src, dst, {}, elems_per_block, device);
           },
           py::arg("src_ptrs"), py::arg("dst_ptrs"), py::arg("elems_per_block"),
           py::arg("device"), py::call_guard<py::gil_scoped_release>());
     m.def("_dbg_mxfp4_dequant_blocks",
           [](const std::vector<uint64_t>& src, const std::vector<uint64_t>& dst,
              size_t elems_per_block, int device) {
-              mxfp4_blocks_py(false, src, dst, elems_per_block, device);
+              transform_blocks_py("_dbg_mxfp4_dequant_blocks", PageCodec::kMxfp4,
+                                  PageDir::kLoad, src, dst, {}, elems_per_block, device);
           },
           py::arg("src_ptrs"), py::arg("dst_ptrs"), py::arg("elems_per_block"),
           py::arg("device"), py::call_guard<py::gil_scoped_release>());

@@ -39,15 +39,12 @@
 #include <type_traits>
 #include <vector>
 
+#include "../core/page_codec.h"
 #include "../core/utils.h"
 #include "kvmap.h"
 #include "shard.h"
 
 namespace ifs {
-
-// What a stored block holds. The values are the snapshot file's codec word
-// (0 and 1 predate mxfp4), so they never change.
-enum class PageCodec : uint8_t { kNone = 0, kFp8 = 1, kMxfp4 = 2 };
 
 // One stored block. Refcounted: the kv map holds one ref; in-flight reads
 // hold another so purge cannot free memory under an active copy.

@@ -750,26 +750,19 @@ void Server::op_local_write(Conn* c, const LocalView& msg, const ReqCtx& ctx) {
     Shard* shard = shard_for_device(msg.device);
     size_t page = static_cast<size_t>(msg.block_size);
     size_t nb = msg.blocks.size();
-    // fp8 ingest compression (extension): bf16 pages stored at half size
-    // with one scale per page; requires a 16-byte-divisible page.
-    const bool quant = (msg.flags & kLocalFlagQuantFp8) != 0;
-    // mxfp4 ingest compression (extension): bf16 pages stored as e2m1 codes
-    // (page/4 bytes) followed by one e8m0 scale byte per 32 elements
-    // (page/64 bytes); requires whole 32-element groups.
-    const bool mx = (msg.flags & kLocalFlagQuantMxfp4) != 0;
-    if (quant && mx) return reply_local(c, ctx, INVALID_REQ);
-    if (quant && (page % 16 != 0)) return reply_local(c, ctx, INVALID_REQ);
-    if (mx && (page % 64 != 0)) return reply_local(c, ctx, INVALID_REQ);
+    // Ingest compression (extension): the flags pick the stored format, and
+    // its page-size rule and stored size come from core/page_codec.h.
+    PageCodec codec;
+    if (!page_codec_from_flags(msg.flags, &codec)) return reply_local(c, ctx, INVALID_REQ);
+    if (!page_legal(codec, page)) return reply_local(c, ctx, INVALID_REQ);
     // The quantize kernels load 16 bytes per lane: every source page must
     // start 16-byte aligned (pool blocks always do).
-    if (quant || mx) {
+    if (page_codec_transforms(codec)) {
         for (size_t i = 0; i < nb; i++)
             if (reinterpret_cast<uintptr_t>(client_ptr + msg.blocks[i].second) % 16 != 0)
                 return reply_local(c, ctx, INVALID_REQ);
     }
-    const size_t stored = quant ? page / 2 : mx ? page / 4 + page / 64 : page;
-    const PageCodec codec =
-        quant ? PageCodec::kFp8 : mx ? PageCodec::kMxfp4 : PageCodec::kNone;
+    const size_t stored = stored_bytes(codec, page);
 
     // Phase A — dedup check only (shared stripe locks, prefetch-pipelined).
     // The authoritative first-write-wins decision happens at the insert pass
@@ -833,14 +826,12 @@ void Server::op_local_write(Conn* c, const LocalView& msg, const ReqCtx& ctx) {
     job.bytes_per_block = page;
     job.src.reserve(n_fresh);
     job.dst.reserve(n_fresh);
-    auto scales_out =
-        quant ? std::make_shared<std::vector<float>>(n_fresh, 1.f) : nullptr;
-    if (quant) {
-        job.xform = Shard::CopyJob::Xform::kQuantBf16Fp8;
-        job.scales_out = scales_out;
-    } else if (mx) {
-        job.xform = Shard::CopyJob::Xform::kQuantBf16Mxfp4;
-    }
+    auto scales_out = page_codec_info(codec).page_scale
+                          ? std::make_shared<std::vector<float>>(n_fresh, 1.f)
+                          : nullptr;
+    job.codec = codec;
+    job.dir = PageDir::kStore;
+    job.scales = scales_out;
     for (size_t i = 0; i < n_fresh; i++) {
         auto* e = slab_batch.make();
         e->ptr = slots[i].first;
@@ -978,8 +969,8 @@ void Server::op_local_read(Conn* c, const LocalView& msg, const ReqCtx& ctx) {
     // traffic through one GPU's remote-read path and its own CUs.
     // IFS_CROSS_COPY=reader flips to pull for topologies where the owner
     // GPUs are compute-saturated; it requires a shard on the reader's GPU.
-    // fp8- and mxfp4-compressed entries go into separate dequantizing jobs,
-    // one group per codec, so one read may mix plain, fp8 and mxfp4 keys.
+    // Compressed entries go into separate dequantizing jobs, one per
+    // (executing shard, codec), so one read may mix plain, fp8 and mxfp4 keys.
     static const bool cross_pull = [] {
         const char* v = getenv("IFS_CROSS_COPY");
         return v && std::string(v) == "reader";
@@ -992,9 +983,9 @@ void Server::op_local_read(Conn* c, const LocalView& msg, const ReqCtx& ctx) {
     auto exec_shard = [&](Shard* owner) {
         return (reader_shard && owner->device() != msg.device) ? reader_shard : owner;
     };
-    std::map<Shard*, Shard::CopyJob> jobs;
-    std::map<Shard*, Shard::CopyJob> qjobs;
-    std::map<Shard*, Shard::CopyJob> mxjobs;
+    std::map<std::pair<Shard*, PageCodec>, Shard::CopyJob> jobs;
+    std::pair<Shard*, PageCodec> last_key;
+    Shard::CopyJob* last_job = nullptr;  // map nodes do not move
     auto held = std::make_shared<std::vector<Ref<BlockEntry>>>();
     held->reserve(msg.blocks.size());
     uint64_t read_tick = index_.tick();
@@ -1011,25 +1002,32 @@ void Server::op_local_read(Conn* c, const LocalView& msg, const ReqCtx& ctx) {
             }
             BlockEntry* e = v->get();
             e->last_access.store(read_tick, std::memory_order_relaxed);
-            // fp8 entries: the page must be the written size, and the
-            // dequantize kernel stores 16 bytes per lane into the client.
-            // mxfp4 entries likewise: stored = 17/64 of the page.
-            const bool fp8 = e->codec == PageCodec::kFp8;
-            const bool mx = e->codec == PageCodec::kMxfp4;
-            if ((fp8 && e->size * 2 != page) || (mx && e->size * 64 != page * 17) ||
-                ((fp8 || mx) &&
+            // Compressed entries: the page must be the written size, and
+            // the dequantize kernels store 16 bytes per lane into the client.
+            if (page_codec_transforms(e->codec) &&
+                (!stored_matches(e->codec, e->size, page) ||
                  reinterpret_cast<uintptr_t>(client_ptr + b.second) % 16 != 0)) {
                 err = INVALID_REQ;
                 return false;
             }
-            auto& job = (fp8 ? qjobs : mx ? mxjobs : jobs)[exec_shard(e->shard)];
-            job.bytes_per_block = page;
-            if (fp8) {
-                job.xform = Shard::CopyJob::Xform::kDequantFp8Bf16;
-                job.scales_in.push_back(e->scale);
-            } else if (mx) {
-                job.xform = Shard::CopyJob::Xform::kDequantMxfp4Bf16;
+            // This runs per block under the stripe lock, where a few ns show
+            // in the headline rate: a run of blocks of one (shard, codec)
+            // reuses its job, and only a new job reads the codec table.
+            const std::pair<Shard*, PageCodec> key{exec_shard(e->shard), e->codec};
+            if (!last_job || key != last_key) {
+                auto [it, fresh] = jobs.try_emplace(key);
+                if (fresh) {
+                    it->second.bytes_per_block = page;
+                    it->second.codec = e->codec;
+                    it->second.dir = PageDir::kLoad;
+                    if (page_codec_info(e->codec).page_scale)
+                        it->second.scales = std::make_shared<std::vector<float>>();
+                }
+                last_key = key;
+                last_job = &it->second;
             }
+            Shard::CopyJob& job = *last_job;
+            if (job.scales) job.scales->push_back(e->scale);
             job.src.push_back(reinterpret_cast<uint64_t>(e->ptr));
             job.dst.push_back(reinterpret_cast<uint64_t>(client_ptr + b.second));
             held->push_back(*v);
@@ -1041,14 +1039,11 @@ void Server::op_local_read(Conn* c, const LocalView& msg, const ReqCtx& ctx) {
     n_reads_.fetch_add(1);
     bytes_out_.fetch_add(msg.blocks.size() * page);
     bool sync_resp = (msg.flags & kLocalFlagSyncResponse) != 0;
-    if (jobs.empty() && qjobs.empty() && mxjobs.empty())
-        return reply_local(c, ctx, sync_resp ? FINISH : TASK_ACCEPTED);
+    if (jobs.empty()) return reply_local(c, ctx, sync_resp ? FINISH : TASK_ACCEPTED);
 
     c->remain.fetch_add(1);
     c->ref();
-    auto pending =
-        std::make_shared<std::atomic<int>>(
-            static_cast<int>(jobs.size() + qjobs.size() + mxjobs.size()));
+    auto pending = std::make_shared<std::atomic<int>>(static_cast<int>(jobs.size()));
     auto all_ok = std::make_shared<std::atomic<bool>>(true);
     auto submit_one = [&](Shard* shard, Shard::CopyJob& job) -> bool {
         Shard::CopyJob j = std::move(job);
@@ -1083,12 +1078,8 @@ void Server::op_local_read(Conn* c, const LocalView& msg, const ReqCtx& ctx) {
         }
         return true;
     };
-    for (auto& [shard, job] : jobs)
-        if (!submit_one(shard, job)) return;
-    for (auto& [shard, job] : qjobs)
-        if (!submit_one(shard, job)) return;
-    for (auto& [shard, job] : mxjobs)
-        if (!submit_one(shard, job)) return;
+    for (auto& [key, job] : jobs)
+        if (!submit_one(key.first, job)) return;
     if (dbg && msg.blocks.size() > 256)
         fprintf(stderr, "[rdbg] read n=%zu collect=%.0f submit=%.0f\n", msg.blocks.size(),
                 us(tr0, tcol), us(tcol, Clock::now()));
@@ -1826,7 +1817,7 @@ namespace {
 constexpr uint64_t kSnapMagic = 0x53494653504e3150ull;  // "SIFSPN1P"
 struct SnapEntryHdr {
     uint32_t key_len;
-    uint32_t fp8;   // PageCodec: 0 plain, 1 fp8, 2 mxfp4 (the name predates 2)
+    uint32_t codec;  // PageCodec value: 0 plain, 1 fp8, 2 mxfp4
     uint64_t size;  // stored bytes
     float scale;
     uint32_t _pad;
@@ -1894,7 +1885,7 @@ bool Server::restore(const std::string& path, std::pair<size_t, size_t>* out) {
     for (uint64_t i = 0; i < count && ok; i++) {
         SnapEntryHdr h{};
         if (fread(&h, sizeof(h), 1, f) != 1 || h.key_len > 4096 || h.size > (1u << 30) ||
-            h.fp8 > static_cast<uint32_t>(PageCodec::kMxfp4)) {
+            !page_codec_known(h.codec)) {
             ok = false;
             break;
         }
@@ -1927,7 +1918,7 @@ bool Server::restore(const std::string& path, std::pair<size_t, size_t>* out) {
         e->size = h.size;
         e->pool_idx = pool_idx;
         e->shard = shard;
-        e->codec = static_cast<PageCodec>(h.fp8);
+        e->codec = static_cast<PageCodec>(h.codec);
         e->scale = h.scale;
         e->born_sec = KvIndex::now_sec();
         e->committed = true;

@@ -219,6 +219,10 @@ bool Shard::submit_copy(CopyJob&& job) {
         if (job.done) job.done(true);
         return true;
     }
+    const bool transforms = page_codec_transforms(job.codec);
+    // A codec with a per-page scale needs one scale slot per block.
+    const bool page_scale = page_codec_info(job.codec).page_scale;
+    if (page_scale && (!job.scales || job.scales->size() < job.scales_off + n)) return false;
 
     // Fan very large jobs out across the stream pool: one 1 GB request as a
     // single kernel leaves other streams idle and interacts badly with
@@ -234,12 +238,10 @@ bool Shard::submit_copy(CopyJob&& job) {
             size_t take = std::min(kFanChunk, n - off);
             CopyJob sub;
             sub.bytes_per_block = job.bytes_per_block;
-            sub.xform = job.xform;
-            sub.scales_out = job.scales_out;
+            sub.codec = job.codec;
+            sub.dir = job.dir;
+            sub.scales = job.scales;
             sub.scales_off = job.scales_off + off;
-            if (!job.scales_in.empty())
-                sub.scales_in.assign(job.scales_in.begin() + static_cast<long>(off),
-                                     job.scales_in.begin() + static_cast<long>(off + take));
             sub.src.assign(job.src.begin() + static_cast<long>(off),
                            job.src.begin() + static_cast<long>(off + take));
             sub.dst.assign(job.dst.begin() + static_cast<long>(off),
@@ -257,7 +259,7 @@ bool Shard::submit_copy(CopyJob&& job) {
     }
 
     if (!on_gpu()) {
-        if (job.xform != CopyJob::Xform::kCopy) return false;  // GPU-only
+        if (transforms) return false;  // GPU-only
         // CPU shard: copies run inline on the caller (loop) thread.
         for (size_t i = 0; i < n; i++)
             memcpy(reinterpret_cast<void*>(job.dst[i]), reinterpret_cast<const void*>(job.src[i]),
@@ -274,7 +276,7 @@ bool Shard::submit_copy(CopyJob&& job) {
     }
     // The fp8 and mxfp4 kernels have no byte fallback: they only ever run
     // aligned.
-    if (!aligned && job.xform != CopyJob::Xform::kCopy) return false;
+    if (!aligned && transforms) return false;
 
     // HIP stream enqueues are thread-safe; each job's ops precede its event
     // in stream order regardless of interleaving with other submitters, so
@@ -308,7 +310,7 @@ bool Shard::submit_copy(CopyJob&& job) {
     StreamCtx& sc = streams_[pick];
 
     // Small aligned batches: descriptors ride in the kernel arguments.
-    if (aligned && n <= 16 && job.xform == CopyJob::Xform::kCopy) {
+    if (aligned && n <= 16 && !transforms) {
         Slot* slot = acquire_slot(sc);
         if (!slot) return false;
         bool ok = gpu::set_device(opt_.device) &&
@@ -344,31 +346,22 @@ bool Shard::submit_copy(CopyJob&& job) {
         // profiles/rocprof_bench_r02.txt).
         const uint64_t* dsrc = slot->h_src;
         const uint64_t* ddst = slot->h_dst;
-        if (job.xform == CopyJob::Xform::kCopy) {
+        if (!transforms) {
             ok = ok && gpu::launch_copy_blocks(opt_.device, sc.stream, dsrc, ddst,
                                                static_cast<int>(take), job.bytes_per_block,
                                                aligned);
-        } else if (job.xform == CopyJob::Xform::kQuantBf16Fp8) {
-            // The kernel writes each block's scale straight into pinned
-            // h_scale (one 4 B write per block) — no D2H needed.
-            ok = ok && gpu::launch_quant_blocks(opt_.device, sc.stream, dsrc, ddst,
-                                                slot->h_scale, static_cast<int>(take),
-                                                job.bytes_per_block / 2);
-        } else if (job.xform == CopyJob::Xform::kDequantFp8Bf16) {
-            // (kernel reads desc + scale once per WG)
-            memcpy(slot->h_scale, job.scales_in.data() + off, take * sizeof(float));
-            ok = ok && gpu::launch_dequant_blocks(opt_.device, sc.stream, dsrc, ddst,
-                                                  slot->h_scale, static_cast<int>(take),
-                                                  job.bytes_per_block / 2);
-        } else if (job.xform == CopyJob::Xform::kQuantBf16Mxfp4) {
-            // Scales live inside the stored block: h_scale is not used.
-            ok = ok && gpu::launch_quant_blocks_mxfp4(opt_.device, sc.stream, dsrc, ddst,
-                                                      static_cast<int>(take),
-                                                      job.bytes_per_block / 2);
-        } else {  // kDequantMxfp4Bf16
-            ok = ok && gpu::launch_dequant_blocks_mxfp4(opt_.device, sc.stream, dsrc, ddst,
-                                                        static_cast<int>(take),
-                                                        job.bytes_per_block / 2);
+        } else {
+            // Per-page scales ride in pinned h_scale: kStore's kernel writes
+            // each block's scale straight into it (one 4 B write per block,
+            // no D2H needed), kLoad's reads desc + scale once per WG. Codecs
+            // that keep their scales inside the stored block ignore it.
+            if (page_scale && job.dir == PageDir::kLoad)
+                memcpy(slot->h_scale, job.scales->data() + job.scales_off + off,
+                       take * sizeof(float));
+            ok = ok && gpu::launch_transform_blocks(opt_.device, sc.stream, job.codec, job.dir,
+                                                    dsrc, ddst, slot->h_scale,
+                                                    static_cast<int>(take),
+                                                    job.bytes_per_block / kPageElemBytes);
         }
         ok = ok && gpu::event_record(slot->event, sc.stream);
         if (!ok) {
@@ -386,10 +379,10 @@ bool Shard::submit_copy(CopyJob&& job) {
         }
         {
             std::lock_guard<std::mutex> lk(sc.mu);
-            bool q = job.xform == CopyJob::Xform::kQuantBf16Fp8;
+            bool q = page_scale && job.dir == PageDir::kStore;
             sc.pending.push_back({slot,
                                   last ? std::move(job.done) : std::function<void(bool)>(),
-                                  q ? job.scales_out : nullptr, job.scales_off + off, take});
+                                  q ? job.scales : nullptr, job.scales_off + off, take});
         }
         sc.task_cv.notify_one();
         off += take;
@@ -472,8 +465,8 @@ void Shard::completion_loop(size_t stream_idx) {
             std::lock_guard<std::mutex> lk(sc.mu);
             for (auto& t : batch) {
                 if (t.slot) {
-                    if (t.scales_out && t.scales_n)
-                        memcpy(t.scales_out->data() + t.scales_off, t.slot->h_scale,
+                    if (t.scales && t.scales_n)
+                        memcpy(t.scales->data() + t.scales_off, t.slot->h_scale,
                                t.scales_n * sizeof(float));
                     t.slot->busy = false;
                 }

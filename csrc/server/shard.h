@@ -43,26 +43,20 @@ class Shard {
    public:
     // Descriptor list: uniform-size block copies src[i] -> dst[i].
     struct CopyJob {
-        // kCopy moves bytes; the fp8 transforms convert while moving
-        // (bytes_per_block is the LOGICAL bf16 size in all modes — the fp8
-        // side of a transform is half that, the mxfp4 side 17/64 of it with
-        // its scales inside the block: no scales_out / scales_in).
-        enum class Xform {
-            kCopy = 0,
-            kQuantBf16Fp8,
-            kDequantFp8Bf16,
-            kQuantBf16Mxfp4,
-            kDequantMxfp4Bf16
-        };
+        // kNone moves bytes; every other codec converts while moving, dst
+        // being the stored block for kStore and the logical page for kLoad
+        // (bytes_per_block is the LOGICAL bf16 size in all modes; the stored
+        // side's size is the codec's, core/page_codec.h).
         std::vector<uint64_t> src;
         std::vector<uint64_t> dst;
         size_t bytes_per_block = 0;
-        Xform xform = Xform::kCopy;
-        // kQuant: per-block scales, written at [scales_off..) before done().
-        std::shared_ptr<std::vector<float>> scales_out;
+        PageCodec codec = PageCodec::kNone;
+        PageDir dir = PageDir::kStore;
+        // Codecs with a per-page scale: block i's scale is
+        // (*scales)[scales_off + i], written before done() by kStore and
+        // read at submit by kLoad. Fan-out sub-jobs share the vector.
+        std::shared_ptr<std::vector<float>> scales;
         size_t scales_off = 0;
-        // kDequant: per-block scale inputs.
-        std::vector<float> scales_in;
         // Completion callback; invoked exactly once from the shard completion
         // thread (GPU) or inline (CPU shard). ok=false means the copy failed.
         std::function<void(bool ok)> done;
@@ -152,9 +146,10 @@ class Shard {
     struct PendingTask {
         Slot* slot;
         std::function<void(bool)> done;  // may be empty for chunked sub-jobs
-        // quant jobs: copy slot->h_scale[0..n) into (*scales_out)[off..)
-        // BEFORE the slot is released (the next submitter reuses h_scale).
-        std::shared_ptr<std::vector<float>> scales_out;
+        // kStore jobs of a per-page-scale codec: copy slot->h_scale[0..n)
+        // into (*scales)[off..) BEFORE the slot is released (the next
+        // submitter reuses h_scale). Null otherwise.
+        std::shared_ptr<std::vector<float>> scales;
         size_t scales_off = 0;
         size_t scales_n = 0;
     };

@@ -359,8 +359,12 @@ class InfinityConnection:
         """Serialize a key list for the write_pages/read_pages blob form."""
         return "\0".join(keys).encode()
 
-    FLAG_QUANT_FP8 = 2  # wire flag: store bf16 pages fp8-compressed
-    FLAG_QUANT_MXFP4 = 4  # wire flag: store bf16 pages as OCP MXFP4
+    # quant mode -> (wire flag, page_size multiple in bf16 elements). The
+    # native codec table (csrc/core/page_codec.h) is the authority;
+    # tests/test_page_codec.py checks that the two agree.
+    QUANT_MODES = {"fp8": (2, 8), "mxfp4": (4, 32)}
+    FLAG_QUANT_FP8 = QUANT_MODES["fp8"][0]  # store bf16 pages fp8-compressed
+    FLAG_QUANT_MXFP4 = QUANT_MODES["mxfp4"][0]  # store bf16 pages as OCP MXFP4
 
     def write_pages(self, cache: torch.Tensor, keys, offsets, page_size: int,
                     sync: bool = False, quant: Optional[str] = None):
@@ -370,8 +374,9 @@ class InfinityConnection:
 
         quant="fp8": store the pages quantized to fp8 e4m3 (one absmax/448
         scale per page) at HALF the HBM footprint; requires a bf16 cache
-        tensor, and reads of these keys dequantize back to bf16
-        transparently. Doubles effective cache capacity at ~3-bit mantissa
+        tensor and page_size % 8 == 0 (ValueError otherwise, like every
+        refused quant argument), and reads of these keys dequantize back to
+        bf16 transparently. Doubles effective cache capacity at ~3-bit mantissa
         precision — the usual KV-cache quantization trade.
 
         quant="mxfp4": store the pages as OCP microscaling FP4 — e2m1
@@ -390,17 +395,14 @@ class InfinityConnection:
         self._verify(cache)
         assert self.local_connected, "write_pages uses the local GPU path"
         flags = 0
-        if quant == "mxfp4":
+        if quant is not None:
+            if quant not in self.QUANT_MODES:
+                raise ValueError(f"unsupported quant mode {quant!r}")
+            flags, multiple = self.QUANT_MODES[quant]
             if cache.dtype != torch.bfloat16:
-                raise ValueError("mxfp4 quant requires a bf16 cache")
-            if page_size <= 0 or page_size % 32 != 0:
-                raise ValueError("mxfp4 quant needs page_size % 32 == 0")
-            flags = self.FLAG_QUANT_MXFP4
-        elif quant is not None:
-            assert quant == "fp8", f"unsupported quant mode {quant!r}"
-            assert cache.dtype == torch.bfloat16, "fp8 quant requires a bf16 cache"
-            assert page_size % 8 == 0, "fp8 quant needs page_size % 8 == 0"
-            flags = self.FLAG_QUANT_FP8
+                raise ValueError(f"{quant} quant requires a bf16 cache")
+            if page_size <= 0 or page_size % multiple != 0:
+                raise ValueError(f"{quant} quant needs page_size % {multiple} == 0")
         es = cache.element_size()
         offs = np.asarray(offsets, dtype=np.uint64)
         if quant is not None:

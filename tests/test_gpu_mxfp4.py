@@ -108,6 +108,85 @@ def test_mxfp4_mixed_read(gpu_server):
         conn.close()
 
 
+def test_three_codecs_fanout_mixed_read(gpu_server):
+    """4100 fp8, 4100 mxfp4 and 20 plain pages of 32 elements (64 bytes, the
+    smallest page all three formats take), read back by ONE read_pages call
+    that interleaves the kinds, then in reversed order. 4100 blocks make each
+    compressed job fan out into two sub-jobs (4096 blocks each), so the second
+    fp8 sub-job reads the request's scales at a non-zero offset; every fp8 page
+    has its own absmax — a distinct odd factor times a power of two — so a
+    scale taken from the wrong place shows. Bit for bit, no tolerance."""
+    e, nq, npl = 32, 4100, 20
+    g = torch.Generator().manual_seed(12)
+    i = torch.arange(nq)
+    amax = (2.0 * (i % 128) + 1.0) * torch.pow(2.0, (i // 128 - 16).float())
+    assert amax.unique().numel() == nq
+    fp8_pages = ((torch.rand(nq, e, generator=g) - 0.5) * amax[:, None]).to(torch.bfloat16)
+    fp8_pages[i, i % e] = (amax * torch.where(i % 2 == 0, 1.0, -1.0)).to(torch.bfloat16)
+    assert torch.equal(fp8_pages.float().abs().max(dim=1).values, amax)  # exact in bf16
+    mx_pages = _pages(nq, e, 13)
+    plain_pages = _pages(npl, e, 14)
+    pages = torch.cat([fp8_pages, mx_pages, plain_pages])
+    n = pages.shape[0]
+    assert n == 8220
+    codes, scales = fp8_quant_ref(fp8_pages)
+    want = np.concatenate([bf16_bits(fp8_dequant_ref(codes, scales)),
+                           roundtrip_ref(mx_pages).reshape(nq, e), bf16_bits(plain_pages)])
+    # fp8 j, mxfp4 j, and plain j while they last
+    order = [r for j in range(nq)
+             for r in ([j, nq + j] + ([2 * nq + j] if j < npl else []))]
+    assert sorted(order) == list(range(n))
+
+    src = pages.to("cuda:0").reshape(-1)
+    offs = np.arange(n, dtype=np.uint64) * e
+    keys = _keys("mix3", n)
+    conn = local_conn(gpu_server)
+    try:
+        for lo, hi, quant in ((0, nq, "fp8"), (nq, 2 * nq, "mxfp4"), (2 * nq, n, None)):
+            conn.write_pages(src, keys[lo:hi], offs[lo:hi], e, sync=True, quant=quant)
+        dst = torch.zeros_like(src)
+        # page k of dst holds key order[k]
+        conn.read_pages(dst, [keys[r] for r in order], offs, e)
+        conn.sync()
+        assert_bf16_bits_equal(bf16_bits(dst).reshape(n, e), want[order], "interleaved read")
+        dst.zero_()
+        conn.read_pages(dst, [keys[r] for r in order[::-1]], offs, e)
+        conn.sync()
+        assert_bf16_bits_equal(bf16_bits(dst).reshape(n, e), want[order[::-1]],
+                               "interleaved read, reversed")
+    finally:
+        conn.delete_keys(keys)
+        conn.close()
+
+
+@pytest.mark.parametrize("quant", ["fp8", "mxfp4"])
+def test_write_pages_refusals_are_value_errors(gpu_server, quant):
+    """Every quant argument write_pages refuses raises ValueError (checks that
+    survive `python -O`), before anything is sent. This is the client-side
+    half of tests/test_page_codec.py: write_pages wants a GPU tensor and a
+    local connection, so it cannot run there."""
+    conn = local_conn(gpu_server)
+    multiple = conn.QUANT_MODES[quant][1]
+    src = _pages(1, 4 * multiple, 5).to("cuda:0").reshape(-1)
+    assert src.data_ptr() % 16 == 0
+    k = _keys("ve", 1)
+    try:
+        with pytest.raises(ValueError, match="int3"):  # unknown mode
+            conn.write_pages(src, k, [0], multiple, sync=True, quant="int3")
+        with pytest.raises(ValueError, match=quant):  # not a bf16 cache
+            conn.write_pages(src.float(), k, [0], multiple, sync=True, quant=quant)
+        for bad in (0, multiple // 2, multiple + multiple // 2):  # page size
+            with pytest.raises(ValueError, match=quant):
+                conn.write_pages(src, k, [0], bad, sync=True, quant=quant)
+        with pytest.raises(ValueError, match=quant):  # page 8 bytes off a 16-byte boundary
+            conn.write_pages(src, k, [4], multiple, sync=True, quant=quant)
+        with pytest.raises(ValueError, match=quant):  # cache 2 bytes off
+            conn.write_pages(src[1:], k, [0], multiple, sync=True, quant=quant)
+        assert not conn.check_exist(k[0])
+    finally:
+        conn.close()
+
+
 def test_mxfp4_refusals(gpu_server):
     elems = 64
     src = _pages(1, 4 * elems, 3).to("cuda:0").reshape(-1)
