@@ -398,7 +398,8 @@ int ClientConn::rw_local(char op, const std::vector<std::pair<std::string, uint6
 int ClientConn::rw_local_packed(char op, const char* keys_blob, size_t blob_len,
                                 const uint64_t* offsets, size_t n, int block_size,
                                 uintptr_t ptr, int device_id, bool sync_response,
-                                uint64_t* out_ticket, uint32_t extra_flags) {
+                                uint64_t* out_ticket, uint32_t extra_flags,
+                                uint32_t n_segments, uint64_t segment_stride) {
     if (out_ticket) *out_ticket = 0;  // 0 = completed synchronously
     if (!connected_) return -1;
     if (!gpu::available()) {
@@ -447,10 +448,8 @@ int ClientConn::rw_local_packed(char op, const char* keys_blob, size_t blob_len,
     h.rsvd = static_cast<uint32_t>((alloc_size + (1 << 20) - 1) >> 20);
     memcpy(h.ipc, handle.bytes, gpu::kIpcHandleSize);
 
-    std::vector<uint8_t> body(sizeof(h) + n * 8 + blob_len);
-    memcpy(body.data(), &h, sizeof(h));
-    memcpy(body.data() + sizeof(h), offsets, n * 8);
-    memcpy(body.data() + sizeof(h) + n * 8, keys_blob, blob_len);
+    std::vector<uint8_t> body =
+        build_packed_local(h, n_segments, segment_stride, offsets, keys_blob, blob_len);
 
     char wire_op = (op == 'W') ? OP_W_FAST : OP_R_FAST;
     static const bool dbg = getenv("IFS_CLIENT_DEBUG") != nullptr;

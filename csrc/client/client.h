@@ -62,10 +62,15 @@ class ClientConn {
                  int block_size, uintptr_t ptr, int device_id);
     // Fast path: keys as one NUL-separated blob + an offsets array — built
     // straight into the packed wire format (OP_W_FAST / OP_R_FAST).
+    // n_segments > 1: every page is that many equal pieces of the tensor,
+    // segment_stride BYTES apart (segmented pages, core/page_codec.h); with
+    // n_segments == 1 the bytes on the wire are exactly the contiguous ones.
+    // The shm ring and the socket carry the same body.
     int rw_local_packed(char op, const char* keys_blob, size_t blob_len,
                         const uint64_t* offsets, size_t n, int block_size, uintptr_t ptr,
                         int device_id, bool sync_response = false,
-                        uint64_t* out_ticket = nullptr, uint32_t extra_flags = 0);
+                        uint64_t* out_ticket = nullptr, uint32_t extra_flags = 0,
+                        uint32_t n_segments = 1, uint64_t segment_stride = 0);
     // Wait for a ticketed (async shm) op; ticket 0 = already complete.
     int wait_local_ticket(uint64_t ticket);
     int sync_local();

@@ -85,4 +85,37 @@ inline bool stored_matches(PageCodec c, size_t stored, size_t page) {
     return stored * i.den == page * i.num;
 }
 
+// Segmented pages (docs/design.md, "segmented pages"): on the CLIENT side of
+// one request a page may be n_segments equal pieces, piece s starting
+// s * stride_bytes after the page's offset; the stored block is that of their
+// concatenation. The bound is a condition, not a tuning value: with at most
+// 16384 descriptors per launch it keeps every grid far below 2^31 workgroups.
+constexpr uint32_t kMaxPageSegments = 1024;
+
+// Client-side geometry of a request's pages; the default is "contiguous".
+struct PageSegments {
+    uint32_t n = 1;
+    uint64_t stride_bytes = 0;
+};
+
+// The one predicate every layer uses (wire parser, server, shard, launchers,
+// bindings, Python client). n_segments == 1 is the contiguous page and the
+// stride is ignored. Plain pages take any segment size and stride; the
+// transforming kernels move whole 8- (fp8) or 32-element (mxfp4) groups of
+// 16-byte accesses, so a segment is a multiple of the codec's page multiple
+// and the stride keeps every segment 16-byte aligned.
+inline bool segments_legal(PageCodec c, size_t page_bytes, uint64_t n_segments,
+                           uint64_t stride_bytes) {
+    if (n_segments < 1 || n_segments > kMaxPageSegments) return false;
+    if (page_bytes % n_segments != 0) return false;
+    if (n_segments == 1) return true;
+    const size_t seg = page_bytes / n_segments;
+    if (seg == 0 || stride_bytes < seg) return false;  // segments never overlap
+    if (page_codec_transforms(c)) {
+        if (seg % page_codec_info(c).page_multiple != 0) return false;
+        if (stride_bytes % 16 != 0) return false;
+    }
+    return true;
+}
+
 }  // namespace ifs

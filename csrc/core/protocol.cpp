@@ -1,5 +1,9 @@
 #include "protocol.h"
 
+#include <cstring>
+
+#include "page_codec.h"
+
 namespace ifs {
 
 std::string op_name(char op) {
@@ -151,6 +155,63 @@ bool parse_match_request(const uint8_t* buf, size_t len, std::vector<std::string
     auto t = r.root();
     if (!t.valid()) return false;
     *out = t.string_vector(0);
+    return true;
+}
+
+std::vector<uint8_t> build_packed_local(PackedLocalHdr h, uint32_t n_segments,
+                                        uint64_t segment_stride, const uint64_t* offsets,
+                                        const char* keys_blob, size_t blob_len) {
+    const size_t n = h.n_blocks;
+    const bool seg = n_segments != 1;
+    if (seg) h.flags |= kLocalFlagSegmented;
+    const size_t ext = seg ? sizeof(PackedLocalSegExt) : 0;
+    std::vector<uint8_t> body(sizeof(h) + ext + n * 8 + blob_len);
+    memcpy(body.data(), &h, sizeof(h));
+    if (seg) {
+        PackedLocalSegExt e{n_segments, 0, segment_stride};
+        memcpy(body.data() + sizeof(h), &e, sizeof(e));
+    }
+    if (n) memcpy(body.data() + sizeof(h) + ext, offsets, n * 8);
+    if (blob_len) memcpy(body.data() + sizeof(h) + ext + n * 8, keys_blob, blob_len);
+    return body;
+}
+
+bool parse_packed_local(char op, const uint8_t* body, size_t body_len, PackedLocalReq* out) {
+    if (body_len < sizeof(PackedLocalHdr)) return false;
+    PackedLocalHdr& h = out->hdr;
+    memcpy(&h, body, sizeof(h));
+    size_t pos = sizeof(h);
+    out->n_segments = 1;
+    out->segment_stride = 0;
+    if (h.flags & kLocalFlagSegmented) {
+        if (body_len < pos + sizeof(PackedLocalSegExt)) return false;
+        PackedLocalSegExt e;
+        memcpy(&e, body + pos, sizeof(e));
+        pos += sizeof(e);
+        if (e.rsvd != 0) return false;
+        PageCodec codec = PageCodec::kNone;
+        if (op == OP_W_FAST && !page_codec_from_flags(h.flags, &codec)) return false;
+        if (!segments_legal(codec, h.block_size, e.n_segments, e.segment_stride)) return false;
+        out->n_segments = e.n_segments;
+        out->segment_stride = e.segment_stride;
+    }
+    const size_t n = h.n_blocks;
+    const size_t off_end = pos + n * 8;
+    if (body_len < off_end) return false;
+    const uint8_t* offs = body + pos;  // n little-endian u64, any alignment
+    const char* kp = reinterpret_cast<const char*>(body + off_end);
+    const char* kend = reinterpret_cast<const char*>(body + body_len);
+    out->blocks.clear();
+    out->blocks.reserve(n);
+    for (size_t i = 0; i < n; i++) {
+        const char* nul = static_cast<const char*>(memchr(kp, 0, kend - kp));
+        const char* ke = nul ? nul : kend;
+        if (kp > kend || (i + 1 < n && !nul)) return false;
+        uint64_t off;
+        memcpy(&off, offs + i * 8, 8);
+        out->blocks.push_back({std::string_view(kp, ke - kp), off});
+        kp = nul ? nul + 1 : kend;
+    }
     return true;
 }
 

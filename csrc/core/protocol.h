@@ -17,6 +17,8 @@
 
 #include <cstdint>
 #include <string>
+#include <string_view>
+#include <utility>
 #include <vector>
 
 #include "wire.h"
@@ -53,7 +55,8 @@ constexpr char OP_STATS = 'Q';    // server stats JSON over the wire (extension)
 // Packed fast-path local ops (extension): same semantics as OP_W/OP_R but a
 // flat binary layout the hot path can build/parse at memcpy speed — the
 // flatbuffers LocalMetaRequest ops remain accepted for wire compatibility.
-// Body: PackedLocalHdr, u64 offsets[n], NUL-separated key bytes (n keys).
+// Body: PackedLocalHdr, [PackedLocalSegExt when kLocalFlagSegmented is set,]
+// u64 offsets[n], NUL-separated key bytes (n keys).
 constexpr char OP_W_FAST = 'w';
 constexpr char OP_R_FAST = 'r';
 // Shared-memory ring handshake (extension, same-host clients): body is the
@@ -77,6 +80,18 @@ struct PackedLocalHdr {
 #pragma pack(pop)
 static_assert(sizeof(PackedLocalHdr) == 104, "packed local header size");
 
+// Follows PackedLocalHdr when kLocalFlagSegmented is set: the geometry of the
+// request's pages in CLIENT memory (docs/design.md, "segmented pages"). The
+// header keeps its size: its own rsvd word carries the allocation size.
+#pragma pack(push, 1)
+struct PackedLocalSegExt {
+    uint32_t n_segments;
+    uint32_t rsvd;            // 0
+    uint64_t segment_stride;  // bytes from one segment of a page to the next
+};
+#pragma pack(pop)
+static_assert(sizeof(PackedLocalSegExt) == 16, "packed local segment extension size");
+
 // PackedLocalHdr.flags: defer the response until the copy completes (one
 // round trip instead of request-ack + sync).
 constexpr uint32_t kLocalFlagSyncResponse = 1;
@@ -88,6 +103,10 @@ constexpr uint32_t kLocalFlagQuantFp8 = 2;
 // 32 elements inside the stored block, 17/64 of the bf16 bytes (extension,
 // csrc/gpu/mxfp4_codec.h). Setting both quant flags is INVALID_REQ.
 constexpr uint32_t kLocalFlagQuantMxfp4 = 4;
+// Each page is n_segments equal pieces of client memory, segment_stride bytes
+// apart, given by the PackedLocalSegExt that follows the header (extension;
+// packed ops only). The stored block is that of the concatenated page.
+constexpr uint32_t kLocalFlagSegmented = 8;
 
 std::string op_name(char op);
 
@@ -152,6 +171,30 @@ bool parse_allocate_response(const uint8_t* buf, size_t len, std::vector<RemoteB
 
 std::vector<uint8_t> build_match_request(const std::vector<std::string>& keys);
 bool parse_match_request(const uint8_t* buf, size_t len, std::vector<std::string>* out);
+
+// Packed fast-path body (OP_W_FAST / OP_R_FAST). The builder writes the
+// segment extension, and sets kLocalFlagSegmented, only for n_segments > 1:
+// a contiguous request is byte for byte what it was before the extension
+// existed. Offsets are in bytes; keys_blob holds the n NUL-separated keys.
+std::vector<uint8_t> build_packed_local(PackedLocalHdr h, uint32_t n_segments,
+                                        uint64_t segment_stride, const uint64_t* offsets,
+                                        const char* keys_blob, size_t blob_len);
+
+// Parsed view of a packed body: (key, byte offset) per block, the key views
+// pointing into the body. The server moves `blocks` into its request view,
+// so parsing stays one pass and one allocation.
+struct PackedLocalReq {
+    PackedLocalHdr hdr;
+    uint32_t n_segments = 1;
+    uint64_t segment_stride = 0;
+    std::vector<std::pair<std::string_view, uint64_t>> blocks;
+};
+// False (the server answers INVALID_REQ) for a truncated body or extension,
+// a non-zero extension rsvd, more than one quant flag, or a geometry that
+// segments_legal refuses: for the request's codec on OP_W_FAST, for plain
+// pages on OP_R_FAST (the read path re-checks every entry against its own
+// codec once the index has told it what the keys hold).
+bool parse_packed_local(char op, const uint8_t* body, size_t body_len, PackedLocalReq* out);
 
 // Sentinel for duplicate-key allocations: the server returns rkey=0, addr=0
 // for keys that already exist; clients skip writing those blocks (first write

@@ -91,9 +91,17 @@ bool set_device(int dev);
 // avoids any per-launch SDMA upload). Chooses the vectorized 16 B/lane
 // kernel when every pointer and the size are 16-byte aligned, else a
 // byte-granular fallback.
+// Segmented pages (core/page_codec.h): with seg.n > 1 the CLIENT side of every
+// block is seg.n pieces seg.stride_bytes apart, the source for kStore and the
+// destination for kLoad; the pool side stays contiguous. The geometry rides in
+// the kernel arguments: a workgroup is (block, segment, chunk) and still reads
+// its block's descriptor pair once. The vector kernel additionally needs the
+// segment size and the stride to be 16-byte multiples, else the byte kernel
+// runs. seg.n == 1 runs the contiguous kernels; an illegal geometry
+// (segments_legal) returns false before any launch.
 bool launch_copy_blocks(int dev, Stream s, const uint64_t* dev_src_ptrs,
                         const uint64_t* dev_dst_ptrs, int n_blocks, size_t bytes_per_block,
-                        bool aligned16);
+                        bool aligned16, PageSegments seg = {}, PageDir dir = PageDir::kStore);
 
 // Small batches (n <= 16, 16B-aligned): descriptors passed as kernel args
 // from HOST arrays — no device staging needed.
@@ -114,9 +122,15 @@ bool launch_copy_blocks_inline(int dev, Stream s, const uint64_t* src_ptrs,
 //    e2m1 codes, two per byte, then one e8m0 scale byte per 32 elements. The
 //    scales live inside the block, so dev_scales is ignored.
 //    elems_per_block % 32 == 0 (checked here).
+// Segmented pages: with seg.n > 1 the bf16 side (source of kStore,
+// destination of kLoad) is segmented as for launch_copy_blocks; the stored
+// block is byte-identical to the contiguous page's. fp8 keeps ONE scale over
+// all segments; mxfp4 indexes codes and scale bytes by the page-global unit.
+// Segment and stride rules: segments_legal (checked here).
 bool launch_transform_blocks(int dev, Stream s, PageCodec codec, PageDir dir,
                              const uint64_t* dev_src_ptrs, const uint64_t* dev_dst_ptrs,
-                             float* dev_scales, int n_blocks, size_t elems_per_block);
+                             float* dev_scales, int n_blocks, size_t elems_per_block,
+                             PageSegments seg = {});
 // Groups of 32 elements that one workgroup of either mxfp4 kernel covers per
 // loop iteration (four lanes per group).
 constexpr int kMxfp4GroupsPerIter = 64;

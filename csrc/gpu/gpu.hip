@@ -355,23 +355,128 @@ __global__ void copy_blocks_byte_kernel(const uint64_t* __restrict__ src_ptrs,
 
 // Enough workgroups to fill 256 CUs across 8 XCDs with headroom, but ONE
 // descriptor read per workgroup.
-static uint32_t copy_chunks_per_block(uint64_t units_per_block, int n_blocks, int threads) {
+static uint32_t copy_chunks_per_block(uint64_t units_per_block, uint64_t n_blocks, int threads) {
     uint64_t max_chunks = (units_per_block + threads - 1) / static_cast<uint64_t>(threads);
-    uint64_t want = (4096 + n_blocks - 1) / static_cast<uint64_t>(n_blocks);
+    uint64_t want = (4096 + n_blocks - 1) / n_blocks;
     uint64_t c = std::min<uint64_t>(std::max<uint64_t>(want, 1), max_chunks);
     return static_cast<uint32_t>(std::max<uint64_t>(c, 1));
 }
 
+// --- segmented pages ---------------------------------------------------------
+// The client side of a page is n_segments pieces a fixed stride apart; the
+// pool side is their concatenation (docs/design.md, "segmented pages"). The
+// 2D mapping above becomes (block, segment, chunk): a workgroup decodes its
+// triple ONCE from blockIdx.x, reads block b's descriptor pair once through
+// LDS exactly as block_chunk_descs does, and moves both base pointers to its
+// segment; the unit loop that follows is the contiguous kernels' loop over
+// one segment, with no per-unit division. src_stride / dst_stride are the
+// byte distances between a page's segments on either side: the client's
+// stride on the segmented side, the segment's own (stored) size on the pool
+// side, so the direction costs no branch.
+__device__ __forceinline__ uint32_t block_seg_chunk_descs(const uint64_t* __restrict__ src_ptrs,
+                                                          const uint64_t* __restrict__ dst_ptrs,
+                                                          uint32_t n_segments,
+                                                          uint32_t chunks_per_seg,
+                                                          uint64_t (&sd)[2], uint32_t* seg) {
+    uint32_t per_block = n_segments * chunks_per_seg;
+    uint32_t b = blockIdx.x / per_block;
+    uint32_t r = blockIdx.x - b * per_block;
+    uint32_t s = r / chunks_per_seg;
+    uint32_t chunk = r - s * chunks_per_seg;
+    __shared__ uint64_t lds[2];
+    if (threadIdx.x == 0) {
+        lds[0] = src_ptrs[b];
+        lds[1] = dst_ptrs[b];
+    }
+    __syncthreads();
+    sd[0] = lds[0];
+    sd[1] = lds[1];
+    *seg = s;
+    return chunk;
+}
+
+__global__ void copy_blocks_vec_seg_kernel(const uint64_t* __restrict__ src_ptrs,
+                                           const uint64_t* __restrict__ dst_ptrs,
+                                           uint32_t n_segments, uint32_t chunks_per_seg,
+                                           uint64_t units_per_seg, uint64_t src_stride,
+                                           uint64_t dst_stride) {
+    uint64_t sd[2];
+    uint32_t seg;
+    uint32_t chunk =
+        block_seg_chunk_descs(src_ptrs, dst_ptrs, n_segments, chunks_per_seg, sd, &seg);
+    const uint4* s = reinterpret_cast<const uint4*>(sd[0] + seg * src_stride);
+    uint4* d = reinterpret_cast<uint4*>(sd[1] + seg * dst_stride);
+    uint64_t stride = static_cast<uint64_t>(chunks_per_seg) * blockDim.x;
+    for (uint64_t u = static_cast<uint64_t>(chunk) * blockDim.x + threadIdx.x;
+         u < units_per_seg; u += stride)
+        d[u] = s[u];
+}
+
+__global__ void copy_blocks_byte_seg_kernel(const uint64_t* __restrict__ src_ptrs,
+                                            const uint64_t* __restrict__ dst_ptrs,
+                                            uint32_t n_segments, uint32_t chunks_per_seg,
+                                            uint64_t bytes_per_seg, uint64_t src_stride,
+                                            uint64_t dst_stride) {
+    uint64_t sd[2];
+    uint32_t seg;
+    uint32_t chunk =
+        block_seg_chunk_descs(src_ptrs, dst_ptrs, n_segments, chunks_per_seg, sd, &seg);
+    const uint8_t* s = reinterpret_cast<const uint8_t*>(sd[0] + seg * src_stride);
+    uint8_t* d = reinterpret_cast<uint8_t*>(sd[1] + seg * dst_stride);
+    uint64_t stride = static_cast<uint64_t>(chunks_per_seg) * blockDim.x;
+    for (uint64_t u = static_cast<uint64_t>(chunk) * blockDim.x + threadIdx.x;
+         u < bytes_per_seg; u += stride)
+        d[u] = s[u];
+}
+
+// Grid of a (block, segment, chunk) launch: chunks per segment chosen so that
+// n_blocks * S * chunks meets the same ~4096-workgroup target as the
+// contiguous kernels. False when the grid would not fit (never with at most
+// kMaxPageSegments segments and a slot's worth of descriptors).
+static bool seg_grid(uint64_t units_per_seg, int n_blocks, uint32_t n_segments, int threads,
+                     uint32_t* chunks, uint32_t* grid) {
+    uint64_t rows = static_cast<uint64_t>(n_blocks) * n_segments;
+    *chunks = copy_chunks_per_block(units_per_seg, rows, threads);
+    uint64_t g = rows * *chunks;
+    if (g > 0x7fffffffull) return false;
+    *grid = static_cast<uint32_t>(g);
+    return true;
+}
+
 bool launch_copy_blocks(int dev, Stream stream, const uint64_t* dev_src_ptrs,
                         const uint64_t* dev_dst_ptrs, int n_blocks, size_t bytes_per_block,
-                        bool aligned16) {
+                        bool aligned16, PageSegments seg, PageDir dir) {
     if (n_blocks <= 0 || bytes_per_block == 0) return true;
+    if (!segments_legal(PageCodec::kNone, bytes_per_block, seg.n, seg.stride_bytes)) {
+        snprintf(g_err, sizeof(g_err), "launch_copy_blocks: illegal page segments");
+        return false;
+    }
     HIP_OK(hipSetDevice(dev));
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     // threads=512 measured fastest for the grid-stride uint4 copy on gfx950
     // (90.7 us vs 93.4 us at 256 for 2048x128 KB; scripts/copybench.hip —
     // also faster than hipMemcpy D2D at 98.2 us).
     const int threads = 512;
+    if (seg.n > 1) {
+        const uint64_t seg_bytes = bytes_per_block / seg.n;
+        const bool store = dir == PageDir::kStore;
+        const uint64_t src_stride = store ? seg.stride_bytes : seg_bytes;
+        const uint64_t dst_stride = store ? seg_bytes : seg.stride_bytes;
+        const bool vec = aligned16 && seg_bytes % 16 == 0 && seg.stride_bytes % 16 == 0;
+        const uint64_t units = vec ? seg_bytes / 16 : seg_bytes;
+        uint32_t chunks, grid;
+        if (!seg_grid(units, n_blocks, seg.n, threads, &chunks, &grid)) return false;
+        if (vec)
+            hipLaunchKernelGGL(copy_blocks_vec_seg_kernel, dim3(grid), dim3(threads), 0, s,
+                               dev_src_ptrs, dev_dst_ptrs, seg.n, chunks, units, src_stride,
+                               dst_stride);
+        else
+            hipLaunchKernelGGL(copy_blocks_byte_seg_kernel, dim3(grid), dim3(threads), 0, s,
+                               dev_src_ptrs, dev_dst_ptrs, seg.n, chunks, units, src_stride,
+                               dst_stride);
+        HIP_OK(hipGetLastError());
+        return true;
+    }
     if (aligned16 && bytes_per_block % 16 == 0) {
         uint64_t upb = bytes_per_block / 16;
         uint32_t chunks = copy_chunks_per_block(upb, n_blocks, threads);
@@ -538,14 +643,207 @@ __global__ void dequant_blocks_mxfp4_bf16_kernel(const uint64_t* __restrict__ sr
     }
 }
 
+// --- segmented forms of the four transforming kernels -------------------------
+// The bf16 side is segmented (source of quantize, destination of dequantize);
+// the stored block is byte-identical to the one the contiguous kernel makes
+// of the concatenated page.
+
+// fp8: still one 512-thread workgroup per page, because the scale is the
+// PAGE's: pass 1 takes the absmax over every segment before pass 2 converts
+// any. Segment loop outside, unit loop inside; seg_elems % 8 == 0.
+__global__ void quant_blocks_bf16_fp8_seg_kernel(const uint64_t* __restrict__ src_ptrs,
+                                                 const uint64_t* __restrict__ dst_ptrs,
+                                                 float* __restrict__ scales,
+                                                 uint32_t n_segments, uint64_t seg_elems,
+                                                 uint64_t src_stride) {
+    const uint64_t src = src_ptrs[blockIdx.x];
+    uint2* dst = reinterpret_cast<uint2*>(dst_ptrs[blockIdx.x]);
+    __shared__ uint32_t red[8];  // 512 threads / 64-wide wavefronts
+    __shared__ float scale_sh;
+    uint32_t m = 0;  // largest finite bf16 magnitude, as bits
+    uint64_t n8 = seg_elems / 8;
+    for (uint32_t sg = 0; sg < n_segments; sg++) {
+        const uint4* src4 = reinterpret_cast<const uint4*>(src + sg * src_stride);
+        for (uint64_t u = threadIdx.x; u < n8; u += blockDim.x) {
+            uint4 pk = src4[u];
+            const uint16_t* h = reinterpret_cast<const uint16_t*>(&pk);
+#pragma unroll
+            for (int i = 0; i < 8; i++) m = fp8::absmax_step(m, h[i]);
+        }
+    }
+    for (int off = 32; off; off >>= 1) m = max(m, __shfl_down(m, off, 64));
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t mm = red[0];
+        for (int w = 1; w < static_cast<int>(blockDim.x) / 64; w++) mm = max(mm, red[w]);
+        scale_sh = fp8::scale_from_absmax_bits(mm);
+        scales[blockIdx.x] = scale_sh;
+    }
+    __syncthreads();
+    float inv = 1.f / scale_sh;
+    for (uint32_t sg = 0; sg < n_segments; sg++) {
+        const uint4* src4 = reinterpret_cast<const uint4*>(src + sg * src_stride);
+        uint2* dseg = dst + sg * n8;
+        for (uint64_t u = threadIdx.x; u < n8; u += blockDim.x) {
+            uint4 pk = src4[u];
+            const uint16_t* h = reinterpret_cast<const uint16_t*>(&pk);
+            uint8_t out[8];
+#pragma unroll
+            for (int i = 0; i < 8; i++) {
+                float f = fp8::bits_f32(static_cast<uint32_t>(h[i]) << 16);
+                out[i] = fp8::f32_to_e4m3(f * inv);
+            }
+            dseg[u] = *reinterpret_cast<const uint2*>(out);
+        }
+    }
+}
+
+__global__ void dequant_blocks_fp8_bf16_seg_kernel(const uint64_t* __restrict__ src_ptrs,
+                                                   const uint64_t* __restrict__ dst_ptrs,
+                                                   const float* __restrict__ scales,
+                                                   uint32_t n_segments, uint64_t seg_elems,
+                                                   uint64_t dst_stride) {
+    const uint2* src = reinterpret_cast<const uint2*>(src_ptrs[blockIdx.x]);
+    const uint64_t dst = dst_ptrs[blockIdx.x];
+    float scale = scales[blockIdx.x];
+    uint64_t n8 = seg_elems / 8;
+    for (uint32_t sg = 0; sg < n_segments; sg++) {
+        const uint2* sseg = src + sg * n8;
+        uint4* dst4 = reinterpret_cast<uint4*>(dst + sg * dst_stride);
+        for (uint64_t u = threadIdx.x; u < n8; u += blockDim.x) {
+            uint2 pk = sseg[u];
+            const uint8_t* b = reinterpret_cast<const uint8_t*>(&pk);
+            uint16_t out[8];
+#pragma unroll
+            for (int i = 0; i < 8; i++) out[i] = fp8::decode_to_bf16(b[i], scale);
+            dst4[u] = *reinterpret_cast<const uint4*>(out);
+        }
+    }
+}
+
+// mxfp4: workgroup (b, s, chunk). The bf16 side is indexed by the segment's
+// own unit u, the stored side by the page-global unit s * (seg_elems / 8) + u:
+// codes at 4 * u_global, the scale byte at elems / 2 + (u_global >> 2).
+// seg_elems % 32 == 0 makes seg_elems / 8 a multiple of 4, so u_global and u
+// agree in their low two bits and the quad invariant written above
+// kMxfp4Threads holds inside every segment.
+__global__ void quant_blocks_bf16_mxfp4_seg_kernel(const uint64_t* __restrict__ src_ptrs,
+                                                   const uint64_t* __restrict__ dst_ptrs,
+                                                   uint32_t n_segments, uint32_t chunks_per_seg,
+                                                   uint64_t seg_elems, uint64_t src_stride) {
+    uint64_t sd[2];
+    uint32_t seg;
+    uint32_t chunk =
+        block_seg_chunk_descs(src_ptrs, dst_ptrs, n_segments, chunks_per_seg, sd, &seg);
+    uint64_t n8 = seg_elems / 8;
+    const uint4* src4 = reinterpret_cast<const uint4*>(sd[0] + seg * src_stride);
+    uint32_t* codes = reinterpret_cast<uint32_t*>(sd[1]) + seg * n8;
+    uint8_t* scales =
+        reinterpret_cast<uint8_t*>(sd[1]) + n_segments * seg_elems / 2 + seg * (n8 >> 2);
+    uint64_t stride = static_cast<uint64_t>(chunks_per_seg) * blockDim.x;
+    for (uint64_t u = static_cast<uint64_t>(chunk) * blockDim.x + threadIdx.x; u < n8;
+         u += stride) {
+        uint4 pk = src4[u];
+        const uint16_t* h = reinterpret_cast<const uint16_t*>(&pk);
+        uint32_t key = 0;
+#pragma unroll
+        for (int i = 0; i < 8; i++) key = mxfp4::key_step(key, h[i]);
+        key = max(key, __shfl_xor(key, 1, 64));
+        key = max(key, __shfl_xor(key, 2, 64));
+        uint8_t E = mxfp4::group_exponent(key);
+        uint32_t out = 0;
+#pragma unroll
+        for (int i = 0; i < 8; i++)
+            out |= static_cast<uint32_t>(mxfp4::encode(h[i], E)) << (4 * i);
+        codes[u] = out;
+        if ((u & 3u) == 0) scales[u >> 2] = E;
+    }
+}
+
+__global__ void dequant_blocks_mxfp4_bf16_seg_kernel(const uint64_t* __restrict__ src_ptrs,
+                                                     const uint64_t* __restrict__ dst_ptrs,
+                                                     uint32_t n_segments,
+                                                     uint32_t chunks_per_seg,
+                                                     uint64_t seg_elems, uint64_t dst_stride) {
+    uint64_t sd[2];
+    uint32_t seg;
+    uint32_t chunk =
+        block_seg_chunk_descs(src_ptrs, dst_ptrs, n_segments, chunks_per_seg, sd, &seg);
+    uint64_t n8 = seg_elems / 8;
+    const uint32_t* codes = reinterpret_cast<const uint32_t*>(sd[0]) + seg * n8;
+    const uint8_t* scales =
+        reinterpret_cast<const uint8_t*>(sd[0]) + n_segments * seg_elems / 2 + seg * (n8 >> 2);
+    uint4* dst4 = reinterpret_cast<uint4*>(sd[1] + seg * dst_stride);
+    uint64_t stride = static_cast<uint64_t>(chunks_per_seg) * blockDim.x;
+    for (uint64_t u = static_cast<uint64_t>(chunk) * blockDim.x + threadIdx.x; u < n8;
+         u += stride) {
+        uint32_t pk = codes[u];
+        uint8_t E = scales[u >> 2];  // the quad's four lanes read the same byte
+        uint16_t out[8];
+#pragma unroll
+        for (int i = 0; i < 8; i++)
+            out[i] = mxfp4::decode(static_cast<uint8_t>((pk >> (4 * i)) & 0xfu), E);
+        dst4[u] = *reinterpret_cast<const uint4*>(out);
+    }
+}
+
+// Segmented requests of launch_transform_blocks (seg.n > 1, geometry legal).
+static bool launch_transform_blocks_seg(int dev, hipStream_t s, PageCodec codec, bool store,
+                                        const uint64_t* dev_src_ptrs,
+                                        const uint64_t* dev_dst_ptrs, float* dev_scales,
+                                        int n_blocks, size_t elems_per_block, PageSegments seg) {
+    const uint64_t seg_elems = elems_per_block / seg.n;
+    switch (codec) {
+        case PageCodec::kFp8:
+            HIP_OK(hipSetDevice(dev));
+            if (store)
+                hipLaunchKernelGGL(quant_blocks_bf16_fp8_seg_kernel, dim3(n_blocks), dim3(512),
+                                   0, s, dev_src_ptrs, dev_dst_ptrs, dev_scales, seg.n,
+                                   seg_elems, seg.stride_bytes);
+            else
+                hipLaunchKernelGGL(dequant_blocks_fp8_bf16_seg_kernel, dim3(n_blocks),
+                                   dim3(512), 0, s, dev_src_ptrs, dev_dst_ptrs, dev_scales,
+                                   seg.n, seg_elems, seg.stride_bytes);
+            break;
+        case PageCodec::kMxfp4: {
+            uint32_t chunks, grid;
+            if (!seg_grid(seg_elems / 8, n_blocks, seg.n, kMxfp4Threads, &chunks, &grid))
+                return false;
+            HIP_OK(hipSetDevice(dev));
+            if (store)
+                hipLaunchKernelGGL(quant_blocks_bf16_mxfp4_seg_kernel, dim3(grid),
+                                   dim3(kMxfp4Threads), 0, s, dev_src_ptrs, dev_dst_ptrs, seg.n,
+                                   chunks, seg_elems, seg.stride_bytes);
+            else
+                hipLaunchKernelGGL(dequant_blocks_mxfp4_bf16_seg_kernel, dim3(grid),
+                                   dim3(kMxfp4Threads), 0, s, dev_src_ptrs, dev_dst_ptrs, seg.n,
+                                   chunks, seg_elems, seg.stride_bytes);
+            break;
+        }
+        default:
+            return false;
+    }
+    HIP_OK(hipGetLastError());
+    return true;
+}
+
 // The one entry for every transforming codec (gpu.h). A new codec is a kernel
 // pair above and one case here.
 bool launch_transform_blocks(int dev, Stream stream, PageCodec codec, PageDir dir,
                              const uint64_t* dev_src_ptrs, const uint64_t* dev_dst_ptrs,
-                             float* dev_scales, int n_blocks, size_t elems_per_block) {
+                             float* dev_scales, int n_blocks, size_t elems_per_block,
+                             PageSegments seg) {
     if (n_blocks <= 0) return true;
+    if (!segments_legal(codec, elems_per_block * kPageElemBytes, seg.n, seg.stride_bytes)) {
+        snprintf(g_err, sizeof(g_err), "launch_transform_blocks: illegal page segments");
+        return false;
+    }
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const bool store = dir == PageDir::kStore;
+    if (seg.n > 1)
+        return launch_transform_blocks_seg(dev, s, codec, store, dev_src_ptrs, dev_dst_ptrs,
+                                           dev_scales, n_blocks, elems_per_block, seg);
     switch (codec) {
         case PageCodec::kFp8:
             if (elems_per_block % 8 != 0) return false;

@@ -240,6 +240,90 @@ std::vector<float> transform_blocks_py(const char* what, PageCodec codec, PageDi
     return scales;
 }
 
+// ---- segmented forms (docs/design.md, "segmented pages") ------------------
+// The client side of every block is n_segments pieces segment_stride BYTES
+// apart, the pool side contiguous; descriptors in pinned host memory as above.
+
+PageCodec codec_from_id(const char* what, int codec) {
+    if (codec < 0 || !page_codec_known(static_cast<uint32_t>(codec)))
+        throw std::invalid_argument(std::string(what) + ": unknown codec id");
+    return static_cast<PageCodec>(codec);
+}
+
+void copy_blocks_seg_py(const std::vector<uint64_t>& client, const std::vector<uint64_t>& pool,
+                        size_t bytes_per_block, uint32_t n_segments, uint64_t segment_stride,
+                        bool to_pool, int device, const std::string& path) {
+    const char* what = "_dbg_copy_blocks_seg";
+    require_gpu_and_pairs(what, client, pool);
+    const bool vec = path == "vec";
+    if (!vec && path != "byte")
+        throw std::invalid_argument(std::string(what) + ": path must be vec or byte");
+    if (bytes_per_block == 0) throw std::invalid_argument(std::string(what) + ": empty blocks");
+    if (!segments_legal(PageCodec::kNone, bytes_per_block, n_segments, segment_stride))
+        throw std::invalid_argument(std::string(what) + ": illegal page segments");
+    if (vec && (bytes_per_block % 16 != 0 || (bytes_per_block / n_segments) % 16 != 0 ||
+                (n_segments > 1 && segment_stride % 16 != 0) || !all_aligned16(client, pool)))
+        throw std::invalid_argument(std::string(what) +
+                                    ": vec path needs 16-byte-aligned pointers, segment size "
+                                    "and stride");
+    size_t n = client.size();
+    if (n == 0) return;
+    const std::vector<uint64_t>& src = to_pool ? client : pool;
+    const std::vector<uint64_t>& dst = to_pool ? pool : client;
+    Pinned<uint64_t> h_src(n), h_dst(n);
+    memcpy(h_src.p, src.data(), n * 8);
+    memcpy(h_dst.p, dst.data(), n * 8);
+    ScopedStream st(device);
+    bool ok = gpu::launch_copy_blocks(device, st.s, h_src.p, h_dst.p, static_cast<int>(n),
+                                      bytes_per_block, vec,
+                                      PageSegments{n_segments, segment_stride},
+                                      to_pool ? PageDir::kStore : PageDir::kLoad);
+    bool synced = gpu::stream_sync(st.s);
+    if (!ok || !synced)
+        throw std::runtime_error(std::string(what) + " failed: " + gpu::last_error());
+}
+
+// kStore: src is the segmented bf16 side, dst the stored blocks; kLoad the
+// other way round. Scales as in transform_blocks_py.
+std::vector<float> transform_blocks_seg_py(const char* what, int codec_id, PageDir dir,
+                                           const std::vector<uint64_t>& src,
+                                           const std::vector<uint64_t>& dst,
+                                           std::vector<float> scales, size_t elems_per_block,
+                                           uint32_t n_segments, uint64_t segment_stride,
+                                           int device) {
+    const PageCodec codec = codec_from_id(what, codec_id);
+    if (!page_codec_transforms(codec))
+        throw std::invalid_argument(std::string(what) + ": codec does not transform");
+    const PageCodecInfo& info = page_codec_info(codec);
+    const bool store = dir == PageDir::kStore;
+    require_gpu_and_pairs(what, src, dst);
+    if (elems_per_block == 0 || !page_legal(codec, elems_per_block * kPageElemBytes))
+        throw std::invalid_argument(std::string(what) + ": illegal page size");
+    if (!segments_legal(codec, elems_per_block * kPageElemBytes, n_segments, segment_stride))
+        throw std::invalid_argument(std::string(what) + ": illegal page segments");
+    if (!all_aligned16(src, dst))
+        throw std::invalid_argument(std::string(what) + ": pointers must be 16-byte aligned");
+    size_t n = src.size();
+    if (info.page_scale && !store && scales.size() != n)
+        throw std::invalid_argument(std::string(what) + ": one scale per block");
+    scales.resize(info.page_scale ? n : 0);
+    if (n == 0) return scales;
+    Pinned<uint64_t> h_src(n), h_dst(n);
+    Pinned<float> h_scale(n);
+    memcpy(h_src.p, src.data(), n * 8);
+    memcpy(h_dst.p, dst.data(), n * 8);
+    memcpy(h_scale.p, scales.data(), scales.size() * sizeof(float));
+    ScopedStream st(device);
+    bool ok = gpu::launch_transform_blocks(device, st.s, codec, dir, h_src.p, h_dst.p,
+                                           h_scale.p, static_cast<int>(n), elems_per_block,
+                                           PageSegments{n_segments, segment_stride});
+    bool synced = gpu::stream_sync(st.s);
+    if (!ok || !synced)
+        throw std::runtime_error(std::string(what) + " failed: " + gpu::last_error());
+    memcpy(scales.data(), h_scale.p, scales.size() * sizeof(float));
+    return scales;
+}
+
 // (codec id, stored bytes) of a request with these flags and this logical
 // page size, by the codec table alone (host-only).
 std::pair<int, size_t> page_codec_py(uint32_t flags, size_t page_bytes) {
@@ -330,7 +414,8 @@ PYBIND11_MODULE(_native, m) {
             "rw_local_keys",
             [](ClientConn& c, const std::string& op, py::list keys, py::buffer offsets,
                uint64_t element_size, int block_size, uintptr_t ptr, int device,
-               bool sync_response, uint32_t extra_flags) {
+               bool sync_response, uint32_t extra_flags, uint32_t n_segments,
+               uint64_t segment_stride) {
                 // Build the NUL-joined key blob and byte offsets in C++ —
                 // no Python-side join/numpy work on the hot path.
                 py::buffer_info ob = offsets.request();
@@ -353,16 +438,19 @@ PYBIND11_MODULE(_native, m) {
                 py::gil_scoped_release rel;
                 return c.rw_local_packed(op.empty() ? 'W' : op[0], blob.data(), blob.size(),
                                          byte_offs.data(), n, block_size, ptr, device,
-                                         sync_response, nullptr, extra_flags);
+                                         sync_response, nullptr, extra_flags, n_segments,
+                                         segment_stride * element_size);
             },
             py::arg("op"), py::arg("keys"), py::arg("offsets"), py::arg("element_size"),
             py::arg("block_size"), py::arg("ptr"), py::arg("device"),
-            py::arg("sync_response") = false, py::arg("extra_flags") = 0)
+            py::arg("sync_response") = false, py::arg("extra_flags") = 0,
+            py::arg("n_segments") = 1, py::arg("segment_stride") = 0)
         .def(
             "rw_local_blob",
             [](ClientConn& c, const std::string& op, py::buffer blob, py::buffer offsets,
                uint64_t element_size, int block_size, uintptr_t ptr, int device,
-               bool sync_response, uint32_t extra_flags) {
+               bool sync_response, uint32_t extra_flags, uint32_t n_segments,
+               uint64_t segment_stride) {
                 // Zero-pack fast path: keys as one NUL-separated bytes blob
                 // (engines cache the serialized page-key chain; re-joining
                 // 2k Python strings costs ~30 µs per request otherwise).
@@ -378,15 +466,18 @@ PYBIND11_MODULE(_native, m) {
                 py::gil_scoped_release rel;
                 return c.rw_local_packed(op.empty() ? 'W' : op[0], bp, blen, byte_offs.data(),
                                          n, block_size, ptr, device, sync_response, nullptr,
-                                         extra_flags);
+                                         extra_flags, n_segments,
+                                         segment_stride * element_size);
             },
             py::arg("op"), py::arg("blob"), py::arg("offsets"), py::arg("element_size"),
             py::arg("block_size"), py::arg("ptr"), py::arg("device"),
-            py::arg("sync_response") = false, py::arg("extra_flags") = 0)
+            py::arg("sync_response") = false, py::arg("extra_flags") = 0,
+            py::arg("n_segments") = 1, py::arg("segment_stride") = 0)
         .def(
             "rw_local_blob_async",
             [](ClientConn& c, const std::string& op, py::buffer blob, py::buffer offsets,
-               uint64_t element_size, int block_size, uintptr_t ptr, int device) {
+               uint64_t element_size, int block_size, uintptr_t ptr, int device,
+               uint32_t n_segments, uint64_t segment_stride) {
                 // Ticketed form: push the (sync-response) op and return a
                 // ticket to pass to wait_local_ticket — the engine overlaps
                 // its own work with the copy. Ticket 0 = already complete
@@ -406,12 +497,14 @@ PYBIND11_MODULE(_native, m) {
                     py::gil_scoped_release rel;
                     ret = c.rw_local_packed(op.empty() ? 'R' : op[0], bp, blen,
                                             byte_offs.data(), n, block_size, ptr, device,
-                                            /*sync_response=*/true, &ticket);
+                                            /*sync_response=*/true, &ticket, 0, n_segments,
+                                            segment_stride * element_size);
                 }
                 return py::make_tuple(ret, ticket);
             },
             py::arg("op"), py::arg("blob"), py::arg("offsets"), py::arg("element_size"),
-            py::arg("block_size"), py::arg("ptr"), py::arg("device"))
+            py::arg("block_size"), py::arg("ptr"), py::arg("device"),
+            py::arg("n_segments") = 1, py::arg("segment_stride") = 0)
         .def("wait_local_ticket", &ClientConn::wait_local_ticket,
              py::call_guard<py::gil_scoped_release>())
         .def("sync_local", &ClientConn::sync_local, py::call_guard<py::gil_scoped_release>())
@@ -561,8 +654,105 @@ PYBIND11_MODULE(_native, m) {
           py::arg("elems_per_block"), py::arg("device"),
           py::call_guard<py::gil_scoped_release>());
 
+    // ---- debug/test surface (segmented kernels, launched directly) ----
+    m.def("_dbg_copy_blocks_seg", &copy_blocks_seg_py, py::arg("client_ptrs"),
+          py::arg("pool_ptrs"), py::arg("bytes_per_block"), py::arg("n_segments"),
+          py::arg("segment_stride"), py::arg("to_pool"), py::arg("device"), py::arg("path"),
+          py::call_guard<py::gil_scoped_release>());
+    m.def("_dbg_quant_blocks_seg",
+          [](int codec, const std::vector<uint64_t>& src, const std::vector<uint64_t>& dst,
+             size_t elems_per_block, uint32_t n_segments, uint64_t segment_stride, int device) {
+              return transform_blocks_seg_py("_dbg_quant_blocks_seg", codec, PageDir::kStore,
+                                             src, dst, {}, elems_per_block, n_segments,
+                                             segment_stride, device);
+          },
+          py::arg("codec"), py::arg("src_ptrs"), py::arg("dst_ptrs"),
+          py::arg("elems_per_block"), py::arg("n_segments"), py::arg("segment_stride"),
+          py::arg("device"), py::call_guard<py::gil_scoped_release>());
+    m.def("_dbg_dequant_blocks_seg",
+          [](int codec, const std::vector<uint64_t>& src, const std::vector<uint64_t>& dst,
+             const std::vector<float>& scales, size_t elems_per_block, uint32_t n_segments,
+             uint64_t segment_stride, int device) {
+              transform_blocks_seg_py("_dbg_dequant_blocks_seg", codec, PageDir::kLoad, src,
+                                      dst, scales, elems_per_block, n_segments, segment_stride,
+                                      device);
+          },
+          py::arg("codec"), py::arg("src_ptrs"), py::arg("dst_ptrs"), py::arg("scales"),
+          py::arg("elems_per_block"), py::arg("n_segments"), py::arg("segment_stride"),
+          py::arg("device"), py::call_guard<py::gil_scoped_release>());
+
     // ---- debug/test surface (the codec table: csrc/core/page_codec.h) ----
     m.def("_dbg_page_codec", &page_codec_py, py::arg("flags"), py::arg("page_bytes"));
+    // The segment-geometry predicate, codec by id (0 none, 1 fp8, 2 mxfp4).
+    m.def("_dbg_segments_legal",
+          [](int codec, size_t page_bytes, uint64_t n_segments, uint64_t stride_bytes) {
+              return segments_legal(codec_from_id("_dbg_segments_legal", codec), page_bytes,
+                                    n_segments, stride_bytes);
+          },
+          py::arg("codec"), py::arg("page_bytes"), py::arg("n_segments"),
+          py::arg("stride_bytes"));
+    m.attr("_MAX_PAGE_SEGMENTS") = kMaxPageSegments;
+    // Packed fast-path framing (core/protocol.h), with and without the
+    // segment extension. op is "w" or "r"; offsets are in bytes.
+    m.def("_dbg_build_packed_local",
+          [](int device, int pid, uint64_t base_ptr, uint64_t base_offset, uint32_t block_size,
+             uint32_t flags, uint32_t alloc_mb, py::bytes ipc,
+             const std::vector<uint64_t>& offsets, const std::vector<std::string>& keys,
+             uint32_t n_segments, uint64_t segment_stride) {
+              std::string ipc_s = ipc;
+              if (ipc_s.size() != 64)
+                  throw std::invalid_argument("_dbg_build_packed_local: ipc is 64 bytes");
+              if (offsets.size() != keys.size())
+                  throw std::invalid_argument("_dbg_build_packed_local: one offset per key");
+              PackedLocalHdr h;
+              h.device = device;
+              h.pid = pid;
+              h.base_ptr = base_ptr;
+              h.base_offset = base_offset;
+              h.block_size = block_size;
+              h.n_blocks = static_cast<uint32_t>(keys.size());
+              h.flags = flags;
+              h.rsvd = alloc_mb;
+              memcpy(h.ipc, ipc_s.data(), 64);
+              std::string blob;
+              for (size_t i = 0; i < keys.size(); i++) {
+                  if (i) blob.push_back('\0');
+                  blob.append(keys[i]);
+              }
+              auto v = build_packed_local(h, n_segments, segment_stride, offsets.data(),
+                                          blob.data(), blob.size());
+              return py::bytes(reinterpret_cast<const char*>(v.data()), v.size());
+          },
+          py::arg("device"), py::arg("pid"), py::arg("base_ptr"), py::arg("base_offset"),
+          py::arg("block_size"), py::arg("flags"), py::arg("alloc_mb"), py::arg("ipc"),
+          py::arg("offsets"), py::arg("keys"), py::arg("n_segments") = 1,
+          py::arg("segment_stride") = 0);
+    m.def("_dbg_parse_packed_local", [](const std::string& op, py::bytes data) {
+        std::string s = data;
+        PackedLocalReq r;
+        if (op != "w" && op != "r")
+            throw std::invalid_argument("_dbg_parse_packed_local: op is \"w\" or \"r\"");
+        if (!parse_packed_local(op[0], reinterpret_cast<const uint8_t*>(s.data()), s.size(), &r))
+            throw std::invalid_argument("_dbg_parse_packed_local: INVALID_REQ");
+        py::dict d;
+        d["device"] = r.hdr.device;
+        d["pid"] = r.hdr.pid;
+        d["base_ptr"] = r.hdr.base_ptr;
+        d["base_offset"] = r.hdr.base_offset;
+        d["block_size"] = r.hdr.block_size;
+        d["flags"] = r.hdr.flags;
+        d["alloc_mb"] = r.hdr.rsvd;
+        d["n_segments"] = r.n_segments;
+        d["segment_stride"] = r.segment_stride;
+        py::list offs, keys;
+        for (auto& [key, off] : r.blocks) {
+            offs.append(off);
+            keys.append(py::str(std::string(key)));
+        }
+        d["offsets"] = offs;
+        d["keys"] = keys;
+        return d;
+    });
     // One (name, wire flag, page-size multiple in bf16 elements) per codec.
     m.def("_page_codec_rows", [] {
         std::vector<std::tuple<std::string, uint32_t, size_t>> rows;

@@ -526,14 +526,11 @@ Server::LocalView to_view(const LocalMetaMsg& msg) {
     return v;
 }
 
-// Packed fast-path body: PackedLocalHdr, u64 offsets[n], NUL-separated keys.
-bool parse_packed_local(const uint8_t* body, size_t body_len, Server::LocalView* v) {
-    if (body_len < sizeof(PackedLocalHdr)) return false;
-    PackedLocalHdr h;
-    memcpy(&h, body, sizeof(h));
-    size_t n = h.n_blocks;
-    size_t off_end = sizeof(h) + n * 8;
-    if (body_len < off_end) return false;
+// Packed fast-path body (framing and its refusals: core/protocol.h).
+bool parse_packed_local(char op, const uint8_t* body, size_t body_len, Server::LocalView* v) {
+    PackedLocalReq req;
+    if (!ifs::parse_packed_local(op, body, body_len, &req)) return false;
+    const PackedLocalHdr& h = req.hdr;
     v->device = h.device;
     v->pid = h.pid;
     v->base_ptr = h.base_ptr;
@@ -541,19 +538,11 @@ bool parse_packed_local(const uint8_t* body, size_t body_len, Server::LocalView*
     v->block_size = h.block_size;
     v->flags = h.flags;
     v->alloc_mb = h.rsvd;
+    v->n_segments = req.n_segments;
+    v->segment_stride = req.segment_stride;
     v->ipc = body + offsetof(PackedLocalHdr, ipc);
     v->ipc_len = 64;
-    const uint64_t* offs = reinterpret_cast<const uint64_t*>(body + sizeof(h));
-    const char* kp = reinterpret_cast<const char*>(body + off_end);
-    const char* kend = reinterpret_cast<const char*>(body + body_len);
-    v->blocks.reserve(n);
-    for (size_t i = 0; i < n; i++) {
-        const char* nul = static_cast<const char*>(memchr(kp, 0, kend - kp));
-        const char* ke = nul ? nul : kend;
-        if (kp > kend || (i + 1 < n && !nul)) return false;
-        v->blocks.push_back({std::string_view(kp, ke - kp), offs[i]});
-        kp = nul ? nul + 1 : kend;
-    }
+    v->blocks = std::move(req.blocks);
     return true;
 }
 
@@ -591,13 +580,13 @@ void Server::handle_request(Conn* c, char op, std::vector<uint8_t> body) {
         }
         case OP_W_FAST: {
             LocalView v;
-            if (!parse_packed_local(body.data(), body.size(), &v))
+            if (!parse_packed_local(op, body.data(), body.size(), &v))
                 return send_status(c, INVALID_REQ);
             return op_local_write(c, v, ReqCtx{});
         }
         case OP_R_FAST: {
             LocalView v;
-            if (!parse_packed_local(body.data(), body.size(), &v))
+            if (!parse_packed_local(op, body.data(), body.size(), &v))
                 return send_status(c, INVALID_REQ);
             return op_local_read(c, v, ReqCtx{});
         }
@@ -755,8 +744,13 @@ void Server::op_local_write(Conn* c, const LocalView& msg, const ReqCtx& ctx) {
     PageCodec codec;
     if (!page_codec_from_flags(msg.flags, &codec)) return reply_local(c, ctx, INVALID_REQ);
     if (!page_legal(codec, page)) return reply_local(c, ctx, INVALID_REQ);
+    // Segmented source pages: the geometry rules, the stride's alignment for
+    // transforming codecs among them, are segments_legal's.
+    if (!segments_legal(codec, page, msg.n_segments, msg.segment_stride))
+        return reply_local(c, ctx, INVALID_REQ);
     // The quantize kernels load 16 bytes per lane: every source page must
-    // start 16-byte aligned (pool blocks always do).
+    // start 16-byte aligned (pool blocks always do), and a 16-byte stride
+    // then keeps every segment aligned.
     if (page_codec_transforms(codec)) {
         for (size_t i = 0; i < nb; i++)
             if (reinterpret_cast<uintptr_t>(client_ptr + msg.blocks[i].second) % 16 != 0)
@@ -831,6 +825,8 @@ void Server::op_local_write(Conn* c, const LocalView& msg, const ReqCtx& ctx) {
                           : nullptr;
     job.codec = codec;
     job.dir = PageDir::kStore;
+    job.n_segments = msg.n_segments;
+    job.segment_stride = msg.segment_stride;
     job.scales = scales_out;
     for (size_t i = 0; i < n_fresh; i++) {
         auto* e = slab_batch.make();
@@ -954,6 +950,11 @@ void Server::op_local_read(Conn* c, const LocalView& msg, const ReqCtx& ctx) {
     if (!base) return reply_local(c, ctx, INTERNAL_ERROR);
     uint8_t* client_ptr = static_cast<uint8_t*>(base) + msg.base_offset;
     size_t page = static_cast<size_t>(msg.block_size);
+    // Segmented destination pages. Plain rules here; a compressed entry is
+    // checked against its own codec's rules in the sweep, next to
+    // stored_matches.
+    if (!segments_legal(PageCodec::kNone, page, msg.n_segments, msg.segment_stride))
+        return reply_local(c, ctx, INVALID_REQ);
 
     auto tr0 = Clock::now();
     // Group blocks by the shard whose GPU EXECUTES the copy. For same-GPU
@@ -1006,7 +1007,8 @@ void Server::op_local_read(Conn* c, const LocalView& msg, const ReqCtx& ctx) {
             // the dequantize kernels store 16 bytes per lane into the client.
             if (page_codec_transforms(e->codec) &&
                 (!stored_matches(e->codec, e->size, page) ||
-                 reinterpret_cast<uintptr_t>(client_ptr + b.second) % 16 != 0)) {
+                 reinterpret_cast<uintptr_t>(client_ptr + b.second) % 16 != 0 ||
+                 !segments_legal(e->codec, page, msg.n_segments, msg.segment_stride))) {
                 err = INVALID_REQ;
                 return false;
             }
@@ -1020,6 +1022,8 @@ void Server::op_local_read(Conn* c, const LocalView& msg, const ReqCtx& ctx) {
                     it->second.bytes_per_block = page;
                     it->second.codec = e->codec;
                     it->second.dir = PageDir::kLoad;
+                    it->second.n_segments = msg.n_segments;
+                    it->second.segment_stride = msg.segment_stride;
                     if (page_codec_info(e->codec).page_scale)
                         it->second.scales = std::make_shared<std::vector<float>>();
                 }
@@ -1216,7 +1220,7 @@ void Server::fast_worker_main() {
 void Server::run_fast(FastWork& w) {
     ReqCtx ctx{w.seq, true};
     LocalView v;
-    if (!parse_packed_local(w.body.data(), w.body.size(), &v)) {
+    if (!parse_packed_local(w.op, w.body.data(), w.body.size(), &v)) {
         reply_local(w.c, ctx, INVALID_REQ);
     } else if (w.op == OP_W_FAST) {
         op_local_write(w.c, v, ctx);
@@ -1312,7 +1316,7 @@ void Server::shm_poll_main(ShmPeer* p) {
                         break;
                     }
                     LocalView v;  // overload fallback: handle inline
-                    if (!parse_packed_local(body, h.body_len, &v))
+                    if (!parse_packed_local(op, body, h.body_len, &v))
                         reply_local(c, ctx, INVALID_REQ);
                     else if (op == OP_W_FAST)
                         op_local_write(c, v, ctx);

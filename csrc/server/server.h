@@ -142,6 +142,10 @@ class Server {
         int64_t block_size = 0;
         uint32_t flags = 0;
         uint32_t alloc_mb = 0;  // client allocation size (MB); 0 = unknown
+        // Segmented pages (packed ops only): each page is n_segments pieces
+        // of client memory segment_stride bytes apart; 1 = contiguous.
+        uint32_t n_segments = 1;
+        uint64_t segment_stride = 0;
         const uint8_t* ipc = nullptr;
         size_t ipc_len = 0;
         std::vector<std::pair<std::string_view, uint64_t>> blocks;

@@ -220,6 +220,10 @@ bool Shard::submit_copy(CopyJob&& job) {
         return true;
     }
     const bool transforms = page_codec_transforms(job.codec);
+    if (!segments_legal(job.codec, job.bytes_per_block, job.n_segments, job.segment_stride))
+        return false;
+    const bool segmented = job.n_segments > 1;
+    const PageSegments seg{job.n_segments, segmented ? job.segment_stride : 0};
     // A codec with a per-page scale needs one scale slot per block.
     const bool page_scale = page_codec_info(job.codec).page_scale;
     if (page_scale && (!job.scales || job.scales->size() < job.scales_off + n)) return false;
@@ -240,6 +244,8 @@ bool Shard::submit_copy(CopyJob&& job) {
             sub.bytes_per_block = job.bytes_per_block;
             sub.codec = job.codec;
             sub.dir = job.dir;
+            sub.n_segments = job.n_segments;
+            sub.segment_stride = job.segment_stride;
             sub.scales = job.scales;
             sub.scales_off = job.scales_off + off;
             sub.src.assign(job.src.begin() + static_cast<long>(off),
@@ -261,15 +267,25 @@ bool Shard::submit_copy(CopyJob&& job) {
     if (!on_gpu()) {
         if (transforms) return false;  // GPU-only
         // CPU shard: copies run inline on the caller (loop) thread.
+        // A segmented page: the client side steps by the stride, the pool
+        // side by the segment.
+        const size_t seg_bytes = job.bytes_per_block / seg.n;
+        const uint64_t src_step = job.dir == PageDir::kStore ? seg.stride_bytes : seg_bytes;
+        const uint64_t dst_step = job.dir == PageDir::kStore ? seg_bytes : seg.stride_bytes;
         for (size_t i = 0; i < n; i++)
-            memcpy(reinterpret_cast<void*>(job.dst[i]), reinterpret_cast<const void*>(job.src[i]),
-                   job.bytes_per_block);
+            for (uint32_t sg = 0; sg < seg.n; sg++)
+                memcpy(reinterpret_cast<void*>(job.dst[i] + sg * dst_step),
+                       reinterpret_cast<const void*>(job.src[i] + sg * src_step), seg_bytes);
         if (job.done) job.done(true);
         return true;
     }
 
     // Alignment check for the vectorized kernel.
     bool aligned = job.bytes_per_block % 16 == 0;
+    // Segments of a page start at multiples of the stride and of the segment
+    // size: both must keep the 16-byte alignment too.
+    if (segmented)
+        aligned = aligned && (job.bytes_per_block / seg.n) % 16 == 0 && seg.stride_bytes % 16 == 0;
     if (aligned) {
         for (size_t i = 0; i < n && aligned; i++)
             aligned = (job.src[i] % 16 == 0) && (job.dst[i] % 16 == 0);
@@ -310,7 +326,8 @@ bool Shard::submit_copy(CopyJob&& job) {
     StreamCtx& sc = streams_[pick];
 
     // Small aligned batches: descriptors ride in the kernel arguments.
-    if (aligned && n <= 16 && !transforms) {
+    // (Segmented jobs always use the pinned-descriptor kernels.)
+    if (aligned && n <= 16 && !transforms && !segmented) {
         Slot* slot = acquire_slot(sc);
         if (!slot) return false;
         bool ok = gpu::set_device(opt_.device) &&
@@ -349,7 +366,7 @@ bool Shard::submit_copy(CopyJob&& job) {
         if (!transforms) {
             ok = ok && gpu::launch_copy_blocks(opt_.device, sc.stream, dsrc, ddst,
                                                static_cast<int>(take), job.bytes_per_block,
-                                               aligned);
+                                               aligned, seg, job.dir);
         } else {
             // Per-page scales ride in pinned h_scale: kStore's kernel writes
             // each block's scale straight into it (one 4 B write per block,
@@ -361,7 +378,7 @@ bool Shard::submit_copy(CopyJob&& job) {
             ok = ok && gpu::launch_transform_blocks(opt_.device, sc.stream, job.codec, job.dir,
                                                     dsrc, ddst, slot->h_scale,
                                                     static_cast<int>(take),
-                                                    job.bytes_per_block / kPageElemBytes);
+                                                    job.bytes_per_block / kPageElemBytes, seg);
         }
         ok = ok && gpu::event_record(slot->event, sc.stream);
         if (!ok) {

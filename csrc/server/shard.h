@@ -52,6 +52,11 @@ class Shard {
         size_t bytes_per_block = 0;
         PageCodec codec = PageCodec::kNone;
         PageDir dir = PageDir::kStore;
+        // Segmented pages: the CLIENT side of every block (src for kStore,
+        // dst for kLoad) is n_segments pieces segment_stride bytes apart;
+        // the pool side is contiguous. 1 = contiguous (stride ignored).
+        uint32_t n_segments = 1;
+        uint64_t segment_stride = 0;
         // Codecs with a per-page scale: block i's scale is
         // (*scales)[scales_off + i], written before done() by kStore and
         // read at submit by kLoad. Fan-out sub-jobs share the vector.

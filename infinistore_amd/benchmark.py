@@ -50,6 +50,10 @@ def parse_args():
     p.add_argument("--batch", type=int, default=1)
     p.add_argument("--quant", choices=["fp8", "mxfp4"], default=None,
                    help="store pages fp8- or mxfp4-compressed (local-GPU path, bf16)")
+    p.add_argument("--segments", type=int, default=1,
+                   help="segmented pages (local-GPU path): lay each client "
+                        "tensor out [N, n_pages, page/N] and move every page "
+                        "as N segments a plane apart; 1 = contiguous pages")
     p.add_argument("--verify", action="store_true")
     p.add_argument("--json", action="store_true", help="print a JSON summary")
     p.add_argument("--spawn-server", action="store_true",
@@ -102,6 +106,12 @@ def make_buffers(args, conn, local, device):
         if not local:
             conn.register_mr(srcs[-1])
             conn.register_mr(dsts[-1])
+    if local:
+        # The store's kernels run in another process: the fill kernels above
+        # must have finished before the first request reads the sources. A
+        # contiguous first request only reads the start of a tensor, which
+        # the fill reaches first; a segmented one also reads a plane further.
+        torch.cuda.synchronize()
     return srcs, dsts, blocks_per_sub
 
 
@@ -119,8 +129,16 @@ def run_once(args, conn, local, device, bufs=None):
     keys = [f"{run}-{i}" for i in range(n_blocks)]
     per_step = max(1, n_blocks // args.steps)
 
+    nseg = args.segments
+    seg_elems = page_elems // nseg
+
     def sub_of(i):  # block index -> (tensor index, element offset within it)
-        return i // blocks_per_sub, (i % blocks_per_sub) * page_elems
+        return i // blocks_per_sub, (i % blocks_per_sub) * seg_elems
+
+    def geom(t):  # segment arguments for sub-tensor t: [N, n_pages, page/N]
+        if nseg == 1:
+            return {}
+        return {"segments": nseg, "segment_stride": t.numel() // nseg}
 
     # ---- write (layer-by-layer batches, like prefill; each step's slice
     # lives in ONE sub-tensor by construction) ----
@@ -130,10 +148,10 @@ def run_once(args, conn, local, device, bufs=None):
         t_idx, _ = sub_of(s0)
         pairs = [(keys[i], sub_of(i)[1]) for i in range(s0, hi)]
         if local:
-            if args.quant:
+            if args.quant or nseg > 1:
                 conn.write_pages(srcs[t_idx], [p[0] for p in pairs],
                                  [p[1] for p in pairs], page_elems,
-                                 quant=args.quant)
+                                 quant=args.quant, **geom(srcs[t_idx]))
             else:
                 conn.local_gpu_write_cache(srcs[t_idx], pairs, page_elems)
         else:
@@ -162,7 +180,8 @@ def run_once(args, conn, local, device, bufs=None):
                 offs = np.asarray([sub_of(i)[1] for i in range(c0, c1)],
                                   dtype=np.uint64)
                 tickets.append(conn.read_pages_async(dsts[t_idx], ks, offs,
-                                                     page_elems))
+                                                     page_elems,
+                                                     **geom(dsts[t_idx])))
         for tk in tickets:
             conn.wait_read(tk)
     else:
@@ -177,7 +196,9 @@ def run_once(args, conn, local, device, bufs=None):
 
     if args.verify:
         for a, b in zip(srcs, dsts):
-            assert torch.equal(a.cpu(), b.cpu()), "verification failed"
+            assert _close(a.cpu(), b.cpu(), args.quant), "verification failed"
+        if nseg > 1:
+            _verify_contiguous_read(args, conn, srcs[0], dsts[0].device, keys, page_elems)
 
     # Steady-state footprint: drop this iteration's keys (each iteration
     # writes a fresh key set; an engine similarly evicts finished
@@ -188,6 +209,47 @@ def run_once(args, conn, local, device, bufs=None):
         pass
 
     return total_bytes / w_time / 1e6, total_bytes / r_time / 1e6
+
+
+# Largest absolute error of a value in [0, 1) after a round trip through a
+# codec: fp8 e4m3 with scale absmax/448 is at most half the top binade's step
+# (16/448 < 2^-4 of the page's absmax); mxfp4 is at most the saturation gap
+# of its top binade (2/8 of the group's power-of-two range).
+_QUANT_TOL = {"fp8": 2.0 ** -4, "mxfp4": 0.25}
+
+
+def _close(a, b, quant):
+    """--verify's comparison: exact for plain pages, within the codec's
+    error for compressed ones (the harness data is uniform in [0, 1)).
+    Says where the first difference is."""
+    if quant is None:
+        bad = a != b
+    else:
+        bad = ~((a.float() - b.float()).abs() <= _QUANT_TOL[quant])
+    n_bad = int(bad.sum())
+    if n_bad:
+        first = int(bad.reshape(-1).nonzero()[0])
+        print(f"verify: {n_bad} of {a.numel()} elements differ, first at {first}: "
+              f"{a.reshape(-1)[first].item()} vs {b.reshape(-1)[first].item()}",
+              file=sys.stderr)
+    return n_bad == 0
+
+
+def _verify_contiguous_read(args, conn, src, device, keys, page_elems):
+    """--verify for --segments N > 1, second half: so that a mistake common
+    to the segmented write and the segmented read cannot hide, the first
+    pages read CONTIGUOUSLY must equal the concatenation of their segments
+    in the `[N, n_pages, page/N]` source."""
+    nseg = args.segments
+    n_sub = src.numel() // page_elems
+    k = min(n_sub, 64)
+    flat = torch.zeros(k * page_elems, dtype=src.dtype, device=device)
+    torch.cuda.synchronize()  # the fill must not land after the store's copy
+    conn.read_pages(flat, keys[:k], [i * page_elems for i in range(k)], page_elems)
+    conn.sync()
+    want = src.view(nseg, n_sub, page_elems // nseg)[:, :k].transpose(0, 1).reshape(-1)
+    assert _close(want.cpu(), flat.cpu(), args.quant), \
+        "verification failed (contiguous read of segmented pages)"
 
 
 def run_latency(args, conn, local, device):
@@ -295,6 +357,12 @@ def main():
     args = parse_args()
     if args.shape:
         apply_shape(args)
+    if args.segments != 1:
+        es = 2 if args.quant else 4
+        if not args.local_gpu:
+            raise SystemExit("--segments needs --local-gpu")
+        if args.segments < 1 or ((args.block_size << 10) // es) % args.segments:
+            raise SystemExit("--segments must divide the page's element count")
     if args.spawn_server and args.clients > 1:
         # Keys live until each iteration's trailing delete; size the pool
         # for all clients' live iterations plus slack, capped so the pool +

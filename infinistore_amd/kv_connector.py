@@ -86,14 +86,20 @@ class PagedKVConnector:
 
     # -- prefill side ---------------------------------------------------------
     def save_layer(self, layer: int, kv: torch.Tensor, page_keys: List[str],
-                   page_offsets, page_elems: int):
+                   page_offsets, page_elems: int, segments: int = 1,
+                   segment_stride: int = 0):
         """Store this layer's pages of `kv` (offsets in elements). Call per
         layer as prefill produces them; uploads overlap later layers'
-        compute (writes are async until sync())."""
+        compute (writes are async until sync()). segments / segment_stride:
+        segmented pages, as in InfinityConnection.write_pages (local path
+        only, ValueError on the fabric path)."""
         keys = [self._key(layer, k) for k in page_keys]
         if self.local:
             self.conn.write_pages(kv, keys, page_offsets, page_elems,
-                                  quant=self.quant)
+                                  quant=self.quant, segments=segments,
+                                  segment_stride=segment_stride)
+        elif segments != 1:
+            raise ValueError("segmented pages use the local GPU path")
         else:
             self._ensure_mr(kv)
             es = kv.element_size()
@@ -105,13 +111,22 @@ class PagedKVConnector:
 
     # -- decode side ----------------------------------------------------------
     def load_layer(self, layer: int, kv_out: torch.Tensor, page_keys: List[str],
-                   page_offsets, page_elems: int) -> bool:
+                   page_offsets, page_elems: int, segments: int = 1,
+                   segment_stride: int = 0) -> bool:
         """Gather this layer's cached pages into the engine's KV tensor.
-        Returns False if any page is missing (caller falls back to compute)."""
+        Returns False if any page is missing (caller falls back to compute).
+        segments / segment_stride: as in InfinityConnection.read_pages; a
+        refused geometry raises ValueError."""
         keys = [self._key(layer, k) for k in page_keys]
+        if segments != 1 and not self.local:
+            raise ValueError("segmented pages use the local GPU path")
+        self._check_segments(kv_out, page_offsets, page_elems, segments,
+                             segment_stride)
         try:
             if self.local:
-                self.conn.read_pages(kv_out, keys, page_offsets, page_elems)
+                self.conn.read_pages(kv_out, keys, page_offsets, page_elems,
+                                     segments=segments,
+                                     segment_stride=segment_stride)
             else:
                 self._ensure_mr(kv_out)
                 blocks = [(k, int(o)) for k, o in zip(keys, page_offsets)]
@@ -122,18 +137,24 @@ class PagedKVConnector:
             return False
 
     def load_layer_async(self, layer: int, kv_out: torch.Tensor,
-                         page_keys: List[str], page_offsets, page_elems: int):
+                         page_keys: List[str], page_offsets, page_elems: int,
+                         segments: int = 1, segment_stride: int = 0):
         """Ticketed prefetch (local path): push the gather and return a
         ticket; call wait_load(ticket) before touching kv_out. Lets decode
         overlap the next request's KV fetch with current compute. Returns
         None if any page was missing or the path is unavailable (caller
         falls back to load_layer / recompute)."""
         if not self.local:
+            if segments != 1:
+                raise ValueError("segmented pages use the local GPU path")
             return None
         keys = [self._key(layer, k) for k in page_keys]
+        self._check_segments(kv_out, page_offsets, page_elems, segments,
+                             segment_stride)
         try:
             return self.conn.read_pages_async(kv_out, keys, page_offsets,
-                                              page_elems)
+                                              page_elems, segments=segments,
+                                              segment_stride=segment_stride)
         except Exception:
             return None
 
@@ -151,6 +172,13 @@ class PagedKVConnector:
         return self.conn.delete_keys(keys)
 
     # -- internals ------------------------------------------------------------
+    def _check_segments(self, kv: torch.Tensor, page_offsets, page_elems: int,
+                        segments: int, segment_stride: int):
+        # The loads turn every failure into False / None; a refused geometry
+        # is the caller's mistake and stays a ValueError.
+        self.conn._check_segments(kv.numel(), kv.element_size(), page_offsets,
+                                  page_elems, segments, segment_stride)
+
     def _key(self, layer: int, page_hash: str) -> str:
         return f"{self.model_tag}/L{layer}/{page_hash}"
 

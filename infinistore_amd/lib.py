@@ -366,8 +366,45 @@ class InfinityConnection:
     FLAG_QUANT_FP8 = QUANT_MODES["fp8"][0]  # store bf16 pages fp8-compressed
     FLAG_QUANT_MXFP4 = QUANT_MODES["mxfp4"][0]  # store bf16 pages as OCP MXFP4
 
+    # Segmented pages (csrc/core/page_codec.h, docs/design.md): the most
+    # segments one page may have; tests/test_page_segments.py checks it
+    # against the native constant.
+    MAX_PAGE_SEGMENTS = 1024
+
+    @classmethod
+    def _check_segments(cls, numel: int, element_size: int, offsets, page_size: int,
+                        segments: int, segment_stride: int,
+                        quant: Optional[str] = None) -> None:
+        """Refuse (ValueError) a segmented request the store cannot serve,
+        before anything is sent: segments_legal's rules applied in elements,
+        plus the bound check that keeps every segment inside the tensor.
+        `quant` names the codec whose rules apply (None: plain pages; reads
+        pass None, the server checks each stored page's own codec)."""
+        if segments == 1:
+            return
+        if not 1 <= segments <= cls.MAX_PAGE_SEGMENTS:
+            raise ValueError(f"segments must be in 1..{cls.MAX_PAGE_SEGMENTS}")
+        if page_size <= 0 or page_size % segments != 0:
+            raise ValueError("page_size must be a positive multiple of segments")
+        seg = page_size // segments
+        if segment_stride < seg:
+            raise ValueError("segment_stride is smaller than a segment: the segments "
+                             "of a page would overlap")
+        if quant is not None:
+            multiple = cls.QUANT_MODES[quant][1]
+            if seg % multiple != 0:
+                raise ValueError(f"{quant} quant needs segments of a multiple of "
+                                 f"{multiple} elements")
+            if (segment_stride * element_size) % 16 != 0:
+                raise ValueError(f"{quant} quant needs a segment_stride that is a "
+                                 "multiple of 16 bytes")
+        if len(offsets) and (int(max(offsets)) + (segments - 1) * segment_stride + seg
+                             > numel):
+            raise ValueError("a segmented page extends outside the tensor")
+
     def write_pages(self, cache: torch.Tensor, keys, offsets, page_size: int,
-                    sync: bool = False, quant: Optional[str] = None):
+                    sync: bool = False, quant: Optional[str] = None,
+                    segments: int = 1, segment_stride: int = 0):
         """sync=True completes the write in ONE round trip (the response is
         sent when the copy finishes); sync=False (default) returns after the
         server accepts, so uploads overlap compute — call sync() later.
@@ -391,8 +428,19 @@ class InfinityConnection:
         the group's absmax exponent; +-inf and anything above the group's
         range saturate to +-6 x scale; a group holding a NaN reads back as
         all NaN (e2m1 has no NaN code, so the OCP convention marks the
-        group's scale); -0 keeps its sign."""
+        group's scale); -0 keeps its sign.
+
+        segments=S > 1: each page is S equal pieces of `cache`, piece s
+        starting at offset + s * segment_stride (elements), e.g. S=2 and
+        segment_stride=cache.numel() // 2 for a K/V-split
+        ``[2, num_blocks, ...]`` cache. The stored page is the concatenation
+        of the pieces, byte-identical to a contiguous write of it, so any
+        reader, contiguous or segmented with any S, can fetch it. Local path
+        only; an illegal geometry or a page that leaves the tensor is a
+        ValueError before anything is sent."""
         self._verify(cache)
+        if segments != 1 and not self.local_connected:
+            raise ValueError("segmented pages use the local GPU path")
         assert self.local_connected, "write_pages uses the local GPU path"
         flags = 0
         if quant is not None:
@@ -411,34 +459,48 @@ class InfinityConnection:
                 raise ValueError(
                     f"{quant} quant needs a 16-byte-aligned cache and page offsets "
                     "that are multiples of 8 elements")
+        self._check_segments(cache.numel(), es, offs, page_size, segments,
+                             segment_stride, quant)
         if isinstance(keys, (bytes, bytearray, memoryview)):
             ret = self.conn.rw_local_blob(
                 self.OP_W, keys, offs, es, page_size * es,
                 cache.data_ptr(), _remap_device_id(cache), sync, flags,
+                segments, segment_stride,
             )
         else:
             ret = self.conn.rw_local_keys(
                 self.OP_W, keys, offs, es, page_size * es,
                 cache.data_ptr(), _remap_device_id(cache), sync, flags,
+                segments, segment_stride,
             )
         if ret < 0:
             raise Exception(f"Failed to write to infinistore, ret = {ret}")
         return 0
 
-    def read_pages(self, cache: torch.Tensor, keys, offsets, page_size: int):
+    def read_pages(self, cache: torch.Tensor, keys, offsets, page_size: int,
+                   segments: int = 1, segment_stride: int = 0):
+        """segments / segment_stride: scatter each page into that many equal
+        pieces of `cache` (see write_pages), however the page was written.
+        Local path only."""
         self._verify(cache)
+        if segments != 1 and not self.local_connected:
+            raise ValueError("segmented pages use the local GPU path")
         es = cache.element_size()
         if self.local_connected:
             offs = np.asarray(offsets, dtype=np.uint64)
+            self._check_segments(cache.numel(), es, offs, page_size, segments,
+                                 segment_stride)
             if isinstance(keys, (bytes, bytearray, memoryview)):
                 ret = self.conn.rw_local_blob(
                     self.OP_R, keys, offs, es, page_size * es,
-                    cache.data_ptr(), _remap_device_id(cache),
+                    cache.data_ptr(), _remap_device_id(cache), False, 0,
+                    segments, segment_stride,
                 )
             else:
                 ret = self.conn.rw_local_keys(
                     self.OP_R, keys, offs, es, page_size * es,
-                    cache.data_ptr(), _remap_device_id(cache),
+                    cache.data_ptr(), _remap_device_id(cache), False, 0,
+                    segments, segment_stride,
                 )
         elif self.rdma_connected:
             blocks = [(k, int(o) * es) for k, o in zip(keys, offsets)]
@@ -448,21 +510,27 @@ class InfinityConnection:
         if ret < 0:
             raise Exception(f"Failed to read from infinistore, ret = {ret}")
 
-    def read_pages_async(self, cache: torch.Tensor, keys, offsets, page_size: int):
+    def read_pages_async(self, cache: torch.Tensor, keys, offsets, page_size: int,
+                         segments: int = 1, segment_stride: int = 0):
         """Ticketed read (local path, shm ring): pushes the request and
         returns a ticket; call wait_read(ticket) before using the data. Lets
         an engine overlap its own work (or further requests) with the copy —
         e.g. prefetching the next sequence's KV pages while decoding. Falls
-        back to a blocking read (ticket 0) when the ring is unavailable."""
+        back to a blocking read (ticket 0) when the ring is unavailable.
+        segments / segment_stride as in read_pages."""
         self._verify(cache)
+        if segments != 1 and not self.local_connected:
+            raise ValueError("segmented pages use the local GPU path")
         assert self.local_connected, "read_pages_async uses the local GPU path"
         es = cache.element_size()
         offs = np.asarray(offsets, dtype=np.uint64)
+        self._check_segments(cache.numel(), es, offs, page_size, segments,
+                             segment_stride)
         if not isinstance(keys, (bytes, bytearray, memoryview)):
             keys = self.pack_keys(keys)
         ret, ticket = self.conn.rw_local_blob_async(
             self.OP_R, keys, offs, es, page_size * es,
-            cache.data_ptr(), _remap_device_id(cache),
+            cache.data_ptr(), _remap_device_id(cache), segments, segment_stride,
         )
         if ret < 0:
             raise Exception(f"Failed to read from infinistore, ret = {ret}")

@@ -10,10 +10,22 @@ block tables), which is also what makes it testable here.
 
 Engine model assumed (vLLM-style paged attention):
 
-* per layer, one physical cache tensor laid out block-major:
-  ``cache[layer].view(num_blocks, -1)`` — physical block ``b`` of layer
-  ``l`` occupies elements ``[b*page_elems, (b+1)*page_elems)``. The usual
-  ``[num_blocks, 2, block_tokens, n_kv, head]`` layout satisfies this.
+* per layer, one physical cache tensor in one of two layouts
+  (``kv_layout``):
+
+  - ``"block_major"`` (default): ``cache[layer].view(num_blocks, -1)`` —
+    physical block ``b`` of layer ``l`` occupies elements
+    ``[b*page_elems, (b+1)*page_elems)``. The
+    ``[num_blocks, 2, block_tokens, n_kv, head]`` layout satisfies this.
+  - ``"kv_major"``: ``[2, num_blocks, block_tokens, n_kv, head]``, as
+    FlashAttention-style and several ROCm paged-attention back ends
+    allocate. The K half of block ``b`` occupies elements
+    ``[b*page_elems/2, (b+1)*page_elems/2)`` and its V half lies
+    ``cache.numel()/2`` further on. Each block still travels as ONE page
+    under ONE key: a segmented page of two segments
+    (docs/design.md, "segmented pages"), stored exactly as the
+    block-major page ``cat(K[b], V[b])`` would be — so a prefill engine
+    with one layout and a decode engine with the other share pages.
 * a request's logical page ``p`` lives in physical block
   ``block_table[p]`` (an arbitrary permutation — the adapter maps through
   it on both save and load, so prefill and decode engines can use
@@ -56,11 +68,25 @@ class InfiniStoreKVAdapter:
         local: same-host GPU path (IPC + HIP gather) vs the fabric path.
         quant: "fp8" or "mxfp4" to store pages compressed (bf16 engines
             only; "mxfp4" needs page_elems % 32 == 0).
+        kv_layout: "block_major" or "kv_major" (see the module docstring).
+            page_elems counts K plus V in both. "kv_major" needs the local
+            path (ValueError with local=False).
     """
+
+    KV_LAYOUTS = ("block_major", "kv_major")
 
     def __init__(self, host: str, port: int, model_tag: str, n_layers: int,
                  block_tokens: int, page_elems: int, local: bool = True,
-                 quant: Optional[str] = None):
+                 quant: Optional[str] = None, kv_layout: str = "block_major"):
+        if kv_layout not in self.KV_LAYOUTS:
+            raise ValueError(f"kv_layout must be one of {self.KV_LAYOUTS}")
+        if kv_layout == "kv_major":
+            if not local:
+                raise ValueError('kv_layout="kv_major" uses segmented pages, '
+                                 "which need the local GPU path")
+            if page_elems % 2 != 0:
+                raise ValueError("kv_major needs an even page_elems (K plus V)")
+        self.kv_layout = kv_layout
         self.block_tokens = block_tokens
         self.page_elems = page_elems
         self.n_layers = n_layers
@@ -105,10 +131,9 @@ class InfiniStoreKVAdapter:
         s = skip_leading_pages
         if s >= n_pages:
             return
-        offsets = [int(block_table[p]) * self.page_elems
-                   for p in range(s, n_pages)]
+        offsets = self._offsets(block_table, range(s, n_pages))
         self._conn.save_layer(layer, kv_cache.view(-1), keys[s:], offsets,
-                              self.page_elems)
+                              self.page_elems, **self._geometry(kv_cache))
 
     def wait_for_save(self):
         """Barrier: all save_kv_layer uploads committed (readable by any
@@ -133,13 +158,13 @@ class InfiniStoreKVAdapter:
         if len(keys) > len(block_table):
             raise ValueError(f"block_table has {len(block_table)} entries for "
                              f"{len(keys)} pages")
-        offsets = [int(block_table[p]) * self.page_elems
-                   for p in range(len(keys))]
+        offsets = self._offsets(block_table, range(len(keys)))
         self._load_tickets.clear()
         self._load_fallback.clear()
         for li in range(self.n_layers):
             tk = self._conn.load_layer_async(li, kv_caches[li].view(-1), keys,
-                                             offsets, self.page_elems)
+                                             offsets, self.page_elems,
+                                             **self._geometry(kv_caches[li]))
             if tk is not None:
                 self._load_tickets[li] = tk
             else:  # fabric path (or ring unavailable): blocking load at wait
@@ -156,7 +181,7 @@ class InfiniStoreKVAdapter:
         if fb is not None:
             kv, keys, offsets = fb
             return self._conn.load_layer(layer, kv.view(-1), keys, offsets,
-                                         self.page_elems)
+                                         self.page_elems, **self._geometry(kv))
         return True  # nothing pending for this layer (e.g. 0 pages)
 
     # -- maintenance -----------------------------------------------------------
@@ -165,6 +190,19 @@ class InfiniStoreKVAdapter:
         return self._conn.evict(self._page_keys(token_ids))
 
     # -- internals -------------------------------------------------------------
+    def _offsets(self, block_table: Sequence[int], pages) -> List[int]:
+        """Element offset of each logical page's block (its K half for
+        kv_major) in the flattened layer tensor."""
+        step = self.page_elems // 2 if self.kv_layout == "kv_major" else self.page_elems
+        return [int(block_table[p]) * step for p in pages]
+
+    def _geometry(self, kv_cache: torch.Tensor) -> dict:
+        """Segment arguments for one layer tensor: none for block_major; K
+        and V halves a plane (half the tensor) apart for kv_major."""
+        if self.kv_layout != "kv_major":
+            return {}
+        return {"segments": 2, "segment_stride": kv_cache.numel() // 2}
+
     def _page_keys(self, token_ids: Sequence[int]) -> List[str]:
         ck = tuple(token_ids)
         got = self._key_cache.get(ck)
