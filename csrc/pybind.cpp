@@ -11,7 +11,10 @@
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
+#include <condition_variable>
 #include <memory>
+#include <mutex>
+#include <thread>
 
 #include "client/client.h"
 #include "core/log.h"
@@ -21,6 +24,7 @@
 #include "gpu/fp8_codec.h"
 #include "gpu/mxfp4_codec.h"
 #include "gpu/gpu.h"
+#include "server/completed_prefix.h"
 #include "server/server.h"
 
 namespace py = pybind11;
@@ -336,6 +340,235 @@ std::pair<int, size_t> page_codec_py(uint32_t flags, size_t page_bytes) {
                                     std::to_string(page_codec_info(codec).page_multiple) +
                                     " bytes");
     return {static_cast<int>(codec), stored_bytes(codec, page_bytes)};
+}
+
+// ---- jobs through a real Shard (debug/test surface) -------------------------
+// Builds a Shard with the given stream, slot and descriptor limits, submits
+// the jobs from n_threads threads (job i on thread i % n_threads, copy jobs
+// first, list order within a thread), waits until every job was refused or
+// called back, destroys the Shard and reports what happened to each job.
+// All callbacks point into ShardRun, which the caller (and, after a timeout,
+// the reaper thread) keeps alive until the Shard is gone.
+struct ShardRun {
+    struct Result {
+        bool submitted = false;
+        int done_calls = 0;
+        bool ok = false;
+        std::vector<float> scales;  // the shared vector as done() found it
+    };
+    std::unique_ptr<Shard> shard;
+    std::vector<Shard::CopyJob> copy_jobs;
+    std::vector<Shard::FabricJob> fabric_jobs;
+    std::vector<std::shared_ptr<std::vector<float>>> scales;  // per copy job
+    std::vector<Result> results;  // copy jobs, then fabric jobs
+    std::vector<char> open;       // neither refused nor called back yet
+    std::vector<std::thread> submitters;
+    std::mutex mu;
+    std::condition_variable cv;
+    size_t outstanding = 0;
+    bool reaped = false;
+
+    void close(size_t i) {  // mu held
+        if (!open[i]) return;
+        open[i] = 0;
+        outstanding--;
+        cv.notify_all();
+    }
+    void on_done(size_t i, bool ok) {
+        std::lock_guard<std::mutex> lk(mu);
+        Result& r = results[i];
+        r.done_calls++;
+        r.ok = ok;
+        if (i < scales.size() && scales[i]) r.scales = *scales[i];
+        close(i);
+    }
+    void submit(size_t i) {
+        if (i < copy_jobs.size()) {
+            bool submitted = shard->submit_copy(std::move(copy_jobs[i]));
+            std::lock_guard<std::mutex> lk(mu);
+            results[i].submitted = submitted;
+            if (!submitted) close(i);
+        } else {
+            shard->submit_fabric(std::move(fabric_jobs[i - copy_jobs.size()]));
+            std::lock_guard<std::mutex> lk(mu);
+            results[i].submitted = true;
+        }
+    }
+};
+
+py::tuple shard_run_py(int device, int n_streams, int slots_per_stream,
+                       size_t max_descs_per_slot, const py::list& copy_jobs,
+                       const py::list& fabric_jobs, int n_threads, double timeout_s) {
+    const char* what = "_dbg_shard_run";
+    if (device < -1) throw std::invalid_argument(std::string(what) + ": device is -1 or an ordinal");
+    if (device >= 0 && (!gpu::available() || device >= gpu::device_count()))
+        throw std::runtime_error(std::string(what) + ": no such GPU available");
+    if (n_streams < 1 || n_streams > 8 || slots_per_stream < 1 || slots_per_stream > 64 ||
+        max_descs_per_slot < 1 || max_descs_per_slot > 16384)
+        throw std::invalid_argument(std::string(what) + ": stream, slot or descriptor limit");
+    if (n_threads < 1 || n_threads > 64 || !(timeout_s > 0))
+        throw std::invalid_argument(std::string(what) + ": n_threads in 1..64, timeout_s > 0");
+
+    auto st = std::make_shared<ShardRun>();
+    ShardRun* run = st.get();
+    const size_t n_copy = copy_jobs.size(), n_all = n_copy + fabric_jobs.size();
+    st->results.resize(n_all);
+    st->open.assign(n_all, 1);
+    st->outstanding = n_all;
+    for (size_t i = 0; i < n_copy; i++) {
+        py::tuple t = copy_jobs[i].cast<py::tuple>();
+        if (t.size() != 9) throw std::invalid_argument(std::string(what) + ": copy job of 9");
+        Shard::CopyJob j;
+        j.src = t[0].cast<std::vector<uint64_t>>();
+        j.dst = t[1].cast<std::vector<uint64_t>>();
+        j.bytes_per_block = t[2].cast<size_t>();
+        j.codec = codec_from_id(what, t[3].cast<int>());
+        j.dir = t[4].cast<bool>() ? PageDir::kStore : PageDir::kLoad;
+        j.n_segments = t[5].cast<uint32_t>();
+        j.segment_stride = t[6].cast<uint64_t>();
+        if (!t[7].is_none())
+            j.scales = std::make_shared<std::vector<float>>(t[7].cast<std::vector<float>>());
+        j.scales_off = t[8].cast<size_t>();
+        j.done = [run, i](bool ok) { run->on_done(i, ok); };
+        st->scales.push_back(j.scales);
+        st->copy_jobs.push_back(std::move(j));
+    }
+    // A put travels in `host` (the request body), a get lands in `raw_host`
+    // (the response buffer), as in the server; the caller's buffer is copied
+    // in before and, for a get, back out afterwards.
+    std::vector<py::buffer_info> host_bufs;
+    for (size_t k = 0; k < fabric_jobs.size(); k++) {
+        py::tuple t = fabric_jobs[k].cast<py::tuple>();
+        if (t.size() != 5) throw std::invalid_argument(std::string(what) + ": fabric job of 5");
+        Shard::FabricJob j;
+        j.is_put = t[0].cast<bool>();
+        host_bufs.push_back(t[1].cast<py::buffer>().request(/*writable=*/true));
+        const py::buffer_info& info = host_bufs.back();
+        j.block_ptrs = t[2].cast<std::vector<uint64_t>>();
+        j.host_offsets = t[3].cast<std::vector<size_t>>();
+        j.bytes_per_block = t[4].cast<size_t>();
+        const size_t len = static_cast<size_t>(info.size) * static_cast<size_t>(info.itemsize);
+        if (!PyBuffer_IsContiguous(info.view(), 'C'))
+            throw std::invalid_argument(std::string(what) + ": host buffer must be contiguous");
+        if (j.block_ptrs.size() != j.host_offsets.size())
+            throw std::invalid_argument(std::string(what) + ": one host offset per block");
+        for (size_t off : j.host_offsets)
+            if (off > len || j.bytes_per_block > len - off)
+                throw std::invalid_argument(std::string(what) + ": host offset out of bounds");
+        const uint8_t* p = static_cast<const uint8_t*>(info.ptr);
+        if (j.is_put) {
+            j.host = std::make_shared<std::vector<uint8_t>>(p, p + len);
+        } else {
+            j.raw_host = std::shared_ptr<uint8_t[]>(new uint8_t[len ? len : 1]);
+            memcpy(j.raw_host.get(), p, len);
+        }
+        const size_t i = n_copy + k;
+        j.done = [run, i](bool ok) { run->on_done(i, ok); };
+        st->fabric_jobs.push_back(std::move(j));
+    }
+    std::vector<std::shared_ptr<uint8_t[]>> get_bufs;
+    for (auto& j : st->fabric_jobs) get_bufs.push_back(j.raw_host);
+
+    std::string timed_out;
+    {
+        py::gil_scoped_release rel;
+        ShardOptions opt;
+        opt.device = device;
+        opt.pool_bytes = 4 * opt.block_granule;  // the pool itself is not used
+        opt.n_streams = n_streams;
+        opt.slots_per_stream = slots_per_stream;
+        opt.max_descs_per_slot = max_descs_per_slot;
+        st->shard.reset(new Shard(opt));
+        if (!st->shard->init()) {
+            st->shard.reset();
+            throw std::runtime_error(std::string(what) + ": Shard::init failed");
+        }
+        for (int t = 0; t < n_threads; t++)
+            st->submitters.emplace_back([run, t, n_threads, n_all] {
+                for (size_t i = static_cast<size_t>(t); i < n_all; i += n_threads) run->submit(i);
+            });
+        bool finished;
+        {
+            std::unique_lock<std::mutex> lk(st->mu);
+            finished = st->cv.wait_for(lk, std::chrono::duration<double>(timeout_s),
+                                       [&] { return st->outstanding == 0; });
+            if (!finished)
+                for (size_t i = 0; i < n_all; i++)
+                    if (st->open[i]) timed_out += " " + std::to_string(i);
+        }
+        if (finished) {
+            for (auto& t : st->submitters) t.join();
+            st->shard.reset();  // drains every stream's FIFO
+        } else {
+            // Stop the Shard off this thread: its destructor wakes submitters
+            // blocked on a slot (their submit then returns false) and joins
+            // the completion threads, which cannot end while an event never
+            // fires. Wait for that a bounded time, then report either way.
+            std::thread([st] {
+                st->shard.reset();
+                for (auto& t : st->submitters) t.join();
+                std::lock_guard<std::mutex> lk(st->mu);
+                st->reaped = true;
+                st->cv.notify_all();
+            }).detach();
+            std::unique_lock<std::mutex> lk(st->mu);
+            st->cv.wait_for(lk, std::chrono::seconds(10), [&] { return st->reaped; });
+        }
+    }
+    if (!timed_out.empty())
+        throw std::runtime_error(std::string(what) + ": timed out, jobs outstanding:" + timed_out);
+
+    py::list copy_out, fabric_out;
+    std::lock_guard<std::mutex> lk(st->mu);
+    for (size_t i = 0; i < n_all; i++) {
+        const ShardRun::Result& r = st->results[i];
+        if (i < n_copy) {
+            py::dict d;
+            d["submitted"] = r.submitted;
+            d["done_calls"] = r.done_calls;
+            d["ok"] = r.ok;
+            d["scales"] = py::cast(r.done_calls ? r.scales
+                                                : (st->scales[i] ? *st->scales[i]
+                                                                 : std::vector<float>()));
+            copy_out.append(d);
+        } else {
+            const size_t k = i - n_copy;
+            if (get_bufs[k]) {
+                const py::buffer_info& info = host_bufs[k];
+                memcpy(info.ptr, get_bufs[k].get(),
+                       static_cast<size_t>(info.size) * static_cast<size_t>(info.itemsize));
+            }
+            fabric_out.append(py::make_tuple(r.done_calls, r.ok));
+        }
+    }
+    return py::make_tuple(copy_out, fabric_out);
+}
+
+// Shard::completion_loop's search (server/completed_prefix.h) over a modelled
+// queue: has_slot[i] says whether task i is real; at the k-th question
+// fired_at_query[k] (its last value from then on) real tasks, in FIFO order,
+// have fired. Returns the prefix and the indices asked about, in order.
+std::pair<size_t, std::vector<size_t>> completed_prefix_py(
+    const std::vector<bool>& has_slot, const std::vector<size_t>& fired_at_query) {
+    std::vector<size_t> rank(has_slot.size(), 0);  // real tasks before task i
+    size_t reals = 0;
+    for (size_t i = 0; i < has_slot.size(); i++) {
+        rank[i] = reals;
+        if (has_slot[i]) reals++;
+    }
+    std::vector<size_t> asked;
+    size_t prefix = completed_prefix(
+        has_slot.size(), [&](size_t i) { return static_cast<bool>(has_slot[i]); },
+        [&](size_t i) {
+            if (!has_slot[i])
+                throw std::logic_error("completed_prefix asked about a null-slot task");
+            size_t fired = 0;
+            if (!fired_at_query.empty())
+                fired = fired_at_query[std::min(asked.size(), fired_at_query.size() - 1)];
+            asked.push_back(i);
+            return rank[i] < fired;
+        });
+    return {prefix, asked};
 }
 
 }  // namespace
@@ -692,6 +925,19 @@ PYBIND11_MODULE(_native, m) {
           py::arg("codec"), py::arg("page_bytes"), py::arg("n_segments"),
           py::arg("stride_bytes"));
     m.attr("_MAX_PAGE_SEGMENTS") = kMaxPageSegments;
+    // Jobs through a real Shard at small limits. A copy job is (src_ptrs,
+    // dst_ptrs, bytes_per_block, codec_id, store, n_segments, segment_stride,
+    // scales or None, scales_off), a fabric job (is_put, host buffer,
+    // block_ptrs, host_offsets, bytes_per_block). Returns ([{submitted,
+    // done_calls, ok, scales}], [(done_calls, ok)]); device -1 is a CPU shard.
+    m.def("_dbg_shard_run", &shard_run_py, py::arg("device"), py::arg("n_streams"),
+          py::arg("slots_per_stream"), py::arg("max_descs_per_slot"), py::arg("copy_jobs"),
+          py::arg("fabric_jobs"), py::arg("n_threads"), py::arg("timeout_s"));
+    m.attr("_SHARD_FAN_CHUNK") = Shard::kFanChunk;
+    m.attr("_FAB_STAGE_BYTES") = Shard::kFabStageBytes;
+    m.attr("_FAB_STAGE_DESCS") = Shard::kFabStageDescs;
+    m.def("_dbg_completed_prefix", &completed_prefix_py, py::arg("has_slot"),
+          py::arg("fired_at_query"));
     // Packed fast-path framing (core/protocol.h), with and without the
     // segment extension. op is "w" or "r"; offsets are in bytes.
     m.def("_dbg_build_packed_local",

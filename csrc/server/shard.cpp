@@ -5,6 +5,7 @@
 #include <cstring>
 
 #include "../core/log.h"
+#include "completed_prefix.h"
 
 namespace ifs {
 
@@ -232,7 +233,6 @@ bool Shard::submit_copy(CopyJob&& job) {
     // single kernel leaves other streams idle and interacts badly with
     // concurrent large requests; ~4096-block (512 MB at 128 KB) sub-jobs
     // spread the work and complete independently.
-    constexpr size_t kFanChunk = 4096;
     if (on_gpu() && n > kFanChunk && streams_.size() > 1) {
         size_t n_sub = (n + kFanChunk - 1) / kFanChunk;
         auto pending = std::make_shared<std::atomic<int>>(static_cast<int>(n_sub));
@@ -340,6 +340,7 @@ bool Shard::submit_copy(CopyJob&& job) {
             if (!ok) slot->busy = false;
             sc.pending.push_back({ok ? slot : nullptr, std::move(job.done), nullptr, 0, 0});
         }
+        if (!ok) sc.slot_cv.notify_one();
         sc.task_cv.notify_one();
         return true;
     }
@@ -430,22 +431,11 @@ void Shard::completion_loop(size_t stream_idx) {
                 // traffic at O(log depth) per sweep instead of hammering the
                 // HIP runtime's locks from a per-task poll (which competed
                 // with the 64 handler threads' kernel launches).
-                size_t n = sc.pending.size();
-                size_t done_n = 0;
-                // Null-slot tasks (submit failures) are trivially complete.
-                while (done_n < n && !sc.pending[done_n].slot) done_n++;
-                if (done_n < n) {
-                    size_t lo = done_n, hi = n;  // invariant: [0,lo) complete
-                    while (lo < hi) {
-                        size_t mid = (lo + hi) / 2;
-                        if (!sc.pending[mid].slot ||
-                            gpu::event_query(sc.pending[mid].slot->event))
-                            lo = mid + 1;
-                        else
-                            hi = mid;
-                    }
-                    done_n = lo;
-                }
+                // Null-slot tasks (submit failures) complete with the real
+                // tasks in front of them, never ahead (completed_prefix.h).
+                size_t done_n = completed_prefix(
+                    sc.pending.size(), [&](size_t i) { return sc.pending[i].slot != nullptr; },
+                    [&](size_t i) { return gpu::event_query(sc.pending[i].slot->event); });
                 if (done_n > 0) {
                     for (size_t i = 0; i < done_n; i++) {
                         batch.push_back(std::move(sc.pending.front()));

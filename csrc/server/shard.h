@@ -74,6 +74,14 @@ class Shard {
 
     bool init();  // allocate arena, streams, start completion thread
 
+    // Limits, public so that tests compute their edge shapes from them.
+    // submit_copy cuts a job of more than kFanChunk blocks into sub-jobs of
+    // that many when there is more than one stream; a staged fabric chunk is
+    // at most kFabStageBytes of payload and kFabStageDescs blocks.
+    static constexpr size_t kFanChunk = 4096;
+    static constexpr size_t kFabStageBytes = 32ull << 20;
+    static constexpr size_t kFabStageDescs = 8192;
+
     int device() const { return opt_.device; }
     bool on_gpu() const { return opt_.device >= 0; }
 
@@ -201,8 +209,6 @@ class Shard {
     // per-block synchronous hipMemcpy loop (the reference's hot-loop shape,
     // infinistore.cpp:622-625/747-748, which capped the TCP fabric at
     // ~1.5 GB/s).
-    static constexpr size_t kFabStageBytes = 32ull << 20;
-    static constexpr size_t kFabStageDescs = 8192;
     struct FabBuf {
         uint8_t* h_stage = nullptr;  // pinned payload bounce
         uint8_t* d_stage = nullptr;  // device-side chunk
