@@ -399,9 +399,11 @@ int ClientConn::rw_local_packed(char op, const char* keys_blob, size_t blob_len,
                                 const uint64_t* offsets, size_t n, int block_size,
                                 uintptr_t ptr, int device_id, bool sync_response,
                                 uint64_t* out_ticket, uint32_t extra_flags,
-                                uint32_t n_segments, uint64_t segment_stride) {
+                                uint32_t n_segments, uint64_t segment_stride,
+                                const PackedLocalSliceExt* slice) {
     if (out_ticket) *out_ticket = 0;  // 0 = completed synchronously
     if (!connected_) return -1;
+    if (slice && slice->n_pieces != 0 && op != 'R') return -INVALID_REQ;  // read-only
     if (!gpu::available()) {
         ERROR("local path requires a GPU");
         return -1;
@@ -449,7 +451,7 @@ int ClientConn::rw_local_packed(char op, const char* keys_blob, size_t blob_len,
     memcpy(h.ipc, handle.bytes, gpu::kIpcHandleSize);
 
     std::vector<uint8_t> body =
-        build_packed_local(h, n_segments, segment_stride, offsets, keys_blob, blob_len);
+        build_packed_local(h, n_segments, segment_stride, offsets, keys_blob, blob_len, slice);
 
     char wire_op = (op == 'W') ? OP_W_FAST : OP_R_FAST;
     static const bool dbg = getenv("IFS_CLIENT_DEBUG") != nullptr;

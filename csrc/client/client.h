@@ -66,11 +66,16 @@ class ClientConn {
     // segment_stride BYTES apart (segmented pages, core/page_codec.h); with
     // n_segments == 1 the bytes on the wire are exactly the contiguous ones.
     // The shm ring and the socket carry the same body.
+    // slice (reads only; null or n_pieces == 0: whole pages): fetch that
+    // strided part of every stored page; block_size is then the sliced page,
+    // n_pieces * piece_bytes (sliced reads, core/page_codec.h). A slice on
+    // op 'W' returns -INVALID_REQ without sending anything.
     int rw_local_packed(char op, const char* keys_blob, size_t blob_len,
                         const uint64_t* offsets, size_t n, int block_size, uintptr_t ptr,
                         int device_id, bool sync_response = false,
                         uint64_t* out_ticket = nullptr, uint32_t extra_flags = 0,
-                        uint32_t n_segments = 1, uint64_t segment_stride = 0);
+                        uint32_t n_segments = 1, uint64_t segment_stride = 0,
+                        const PackedLocalSliceExt* slice = nullptr);
     // Wait for a ticketed (async shm) op; ticket 0 = already complete.
     int wait_local_ticket(uint64_t ticket);
     int sync_local();

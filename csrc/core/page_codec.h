@@ -118,4 +118,66 @@ inline bool segments_legal(PageCodec c, size_t page_bytes, uint64_t n_segments,
     return true;
 }
 
+// Sliced reads (docs/design.md, "sliced reads"): on the POOL side of a read a
+// request may take n equal pieces of the stored page, piece p starting at
+// logical byte offset + p * stride; the client receives their concatenation,
+// the sliced page, and client-side PageSegments apply to it as to a whole
+// page. All values are LOGICAL (bf16) bytes for every codec; mapping them to
+// stored bytes is the kernels' business. The bound is a condition, not a
+// tuning value: with at most 16384 descriptors per launch it keeps every grid
+// below 2^31 workgroups.
+constexpr uint32_t kMaxSlicePieces = 4096;
+
+// Pool-side geometry of a READ; n == 0 (the default) is the whole page.
+struct PageSlice {
+    uint32_t n = 0;            // pieces
+    uint64_t page_bytes = 0;   // logical size of the page the key was WRITTEN with
+    uint64_t offset = 0;       // logical byte of piece 0 inside that page
+    uint64_t piece_bytes = 0;  // logical size of one piece
+    uint64_t stride = 0;      // logical bytes between pieces (ignored for n == 1)
+};
+
+// The one predicate for a slice (wire parser, server, shard, launcher,
+// bindings, Python client); a whole-page read (n == 0) never comes here.
+// Pieces never overlap and never leave the written page. A transforming
+// kernel moves whole 8-element lane units and, for mxfp4, whole 32-element
+// groups: offset, piece and stride are multiples of the codec's page
+// multiple. A piece never straddles a client segment (n % S == 0), and the
+// sliced page obeys segments_legal like any other page.
+inline bool slice_legal(PageCodec c, const PageSlice& sl, const PageSegments& seg = {}) {
+    if (sl.n < 1 || sl.n > kMaxSlicePieces) return false;
+    if (sl.piece_bytes == 0) return false;
+    const bool many = sl.n > 1;
+    if (many && sl.stride < sl.piece_bytes) return false;
+    // offset + (n - 1) * stride + piece_bytes <= page_bytes, without overflow
+    if (sl.piece_bytes > sl.page_bytes) return false;
+    uint64_t room = sl.page_bytes - sl.piece_bytes;
+    if (sl.offset > room) return false;
+    room -= sl.offset;
+    if (many && sl.stride > room / (sl.n - 1)) return false;
+    if (page_codec_transforms(c)) {
+        const uint32_t m = page_codec_info(c).page_multiple;
+        if (!page_legal(c, sl.page_bytes)) return false;
+        if (sl.offset % m != 0 || sl.piece_bytes % m != 0) return false;
+        if (many && sl.stride % m != 0) return false;
+    }
+    if (seg.n != 1) {
+        if (seg.n == 0 || sl.n % seg.n != 0) return false;
+        // n * piece_bytes <= page_bytes here, so the product cannot overflow
+        if (!segments_legal(c, sl.n * sl.piece_bytes, seg.n, seg.stride_bytes)) return false;
+    }
+    return true;
+}
+
+// Does the request carry a slice at all?
+inline bool slice_is_set(const PageSlice& sl) { return sl.n != 0; }
+
+// The slice as the wire extension carries it, and back.
+inline PackedLocalSliceExt slice_to_wire(const PageSlice& sl) {
+    return {sl.n, 0, sl.page_bytes, sl.offset, sl.piece_bytes, sl.stride};
+}
+inline PageSlice slice_from_wire(const PackedLocalSliceExt& e) {
+    return {e.n_pieces, e.page_bytes, e.offset, e.piece_bytes, e.stride};
+}
+
 }  // namespace ifs

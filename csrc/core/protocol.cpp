@@ -160,17 +160,22 @@ bool parse_match_request(const uint8_t* buf, size_t len, std::vector<std::string
 
 std::vector<uint8_t> build_packed_local(PackedLocalHdr h, uint32_t n_segments,
                                         uint64_t segment_stride, const uint64_t* offsets,
-                                        const char* keys_blob, size_t blob_len) {
+                                        const char* keys_blob, size_t blob_len,
+                                        const PackedLocalSliceExt* slice) {
     const size_t n = h.n_blocks;
     const bool seg = n_segments != 1;
+    const bool sliced = slice && slice->n_pieces != 0;
     if (seg) h.flags |= kLocalFlagSegmented;
-    const size_t ext = seg ? sizeof(PackedLocalSegExt) : 0;
+    if (sliced) h.flags |= kLocalFlagSliced;
+    const size_t seg_ext = seg ? sizeof(PackedLocalSegExt) : 0;
+    const size_t ext = seg_ext + (sliced ? sizeof(PackedLocalSliceExt) : 0);
     std::vector<uint8_t> body(sizeof(h) + ext + n * 8 + blob_len);
     memcpy(body.data(), &h, sizeof(h));
     if (seg) {
         PackedLocalSegExt e{n_segments, 0, segment_stride};
         memcpy(body.data() + sizeof(h), &e, sizeof(e));
     }
+    if (sliced) memcpy(body.data() + sizeof(h) + seg_ext, slice, sizeof(*slice));
     if (n) memcpy(body.data() + sizeof(h) + ext, offsets, n * 8);
     if (blob_len) memcpy(body.data() + sizeof(h) + ext + n * 8, keys_blob, blob_len);
     return body;
@@ -194,6 +199,22 @@ bool parse_packed_local(char op, const uint8_t* body, size_t body_len, PackedLoc
         if (!segments_legal(codec, h.block_size, e.n_segments, e.segment_stride)) return false;
         out->n_segments = e.n_segments;
         out->segment_stride = e.segment_stride;
+    }
+    out->slice = PackedLocalSliceExt{};
+    if (h.flags & kLocalFlagSliced) {
+        if (op != OP_R_FAST) return false;  // slices are a read-side geometry
+        if (body_len < pos + sizeof(PackedLocalSliceExt)) return false;
+        PackedLocalSliceExt e;
+        memcpy(&e, body + pos, sizeof(e));
+        pos += sizeof(e);
+        if (e.rsvd != 0) return false;
+        // Plain rules, like the segments above; a zero-piece extension fails
+        // slice_legal, so a parsed request is sliced exactly when n_pieces != 0.
+        if (!slice_legal(PageCodec::kNone, slice_from_wire(e),
+                         PageSegments{out->n_segments, out->segment_stride}))
+            return false;
+        if (h.block_size != e.n_pieces * e.piece_bytes) return false;
+        out->slice = e;
     }
     const size_t n = h.n_blocks;
     const size_t off_end = pos + n * 8;

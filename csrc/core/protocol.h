@@ -56,7 +56,8 @@ constexpr char OP_STATS = 'Q';    // server stats JSON over the wire (extension)
 // flat binary layout the hot path can build/parse at memcpy speed — the
 // flatbuffers LocalMetaRequest ops remain accepted for wire compatibility.
 // Body: PackedLocalHdr, [PackedLocalSegExt when kLocalFlagSegmented is set,]
-// u64 offsets[n], NUL-separated key bytes (n keys).
+// [PackedLocalSliceExt when kLocalFlagSliced is set,] u64 offsets[n],
+// NUL-separated key bytes (n keys).
 constexpr char OP_W_FAST = 'w';
 constexpr char OP_R_FAST = 'r';
 // Shared-memory ring handshake (extension, same-host clients): body is the
@@ -92,6 +93,22 @@ struct PackedLocalSegExt {
 #pragma pack(pop)
 static_assert(sizeof(PackedLocalSegExt) == 16, "packed local segment extension size");
 
+// Follows PackedLocalHdr, and PackedLocalSegExt when that is present, when
+// kLocalFlagSliced is set: the POOL-side geometry of a read (core/page_codec.h,
+// PageSlice; docs/design.md, "sliced reads"). All values are logical bytes.
+// The header's block_size is the sliced page: n_pieces * piece_bytes.
+#pragma pack(push, 1)
+struct PackedLocalSliceExt {
+    uint32_t n_pieces;
+    uint32_t rsvd;         // 0
+    uint64_t page_bytes;   // logical size of the page the keys were written with
+    uint64_t offset;       // logical byte of piece 0 inside that page
+    uint64_t piece_bytes;
+    uint64_t stride;       // logical bytes from one piece to the next
+};
+#pragma pack(pop)
+static_assert(sizeof(PackedLocalSliceExt) == 40, "packed local slice extension size");
+
 // PackedLocalHdr.flags: defer the response until the copy completes (one
 // round trip instead of request-ack + sync).
 constexpr uint32_t kLocalFlagSyncResponse = 1;
@@ -107,6 +124,10 @@ constexpr uint32_t kLocalFlagQuantMxfp4 = 4;
 // apart, given by the PackedLocalSegExt that follows the header (extension;
 // packed ops only). The stored block is that of the concatenated page.
 constexpr uint32_t kLocalFlagSegmented = 8;
+// Read n_pieces strided pieces of each stored page instead of the whole page,
+// given by the PackedLocalSliceExt that follows the header and the segment
+// extension (extension; OP_R_FAST only, INVALID_REQ on OP_W_FAST).
+constexpr uint32_t kLocalFlagSliced = 16;
 
 std::string op_name(char op);
 
@@ -176,9 +197,13 @@ bool parse_match_request(const uint8_t* buf, size_t len, std::vector<std::string
 // segment extension, and sets kLocalFlagSegmented, only for n_segments > 1:
 // a contiguous request is byte for byte what it was before the extension
 // existed. Offsets are in bytes; keys_blob holds the n NUL-separated keys.
+// Likewise the slice extension and kLocalFlagSliced are written only for a
+// slice with n_pieces != 0 (its rsvd is written as given, 0 from every real
+// caller); without one the body is what it was before slices existed.
 std::vector<uint8_t> build_packed_local(PackedLocalHdr h, uint32_t n_segments,
                                         uint64_t segment_stride, const uint64_t* offsets,
-                                        const char* keys_blob, size_t blob_len);
+                                        const char* keys_blob, size_t blob_len,
+                                        const PackedLocalSliceExt* slice = nullptr);
 
 // Parsed view of a packed body: (key, byte offset) per block, the key views
 // pointing into the body. The server moves `blocks` into its request view,
@@ -187,13 +212,16 @@ struct PackedLocalReq {
     PackedLocalHdr hdr;
     uint32_t n_segments = 1;
     uint64_t segment_stride = 0;
+    PackedLocalSliceExt slice{};  // n_pieces == 0: whole pages
     std::vector<std::pair<std::string_view, uint64_t>> blocks;
 };
 // False (the server answers INVALID_REQ) for a truncated body or extension,
 // a non-zero extension rsvd, more than one quant flag, or a geometry that
 // segments_legal refuses: for the request's codec on OP_W_FAST, for plain
 // pages on OP_R_FAST (the read path re-checks every entry against its own
-// codec once the index has told it what the keys hold).
+// codec once the index has told it what the keys hold). kLocalFlagSliced is
+// refused on OP_W_FAST; on OP_R_FAST also when block_size is not n_pieces *
+// piece_bytes or slice_legal refuses the geometry under plain rules.
 bool parse_packed_local(char op, const uint8_t* body, size_t body_len, PackedLocalReq* out);
 
 // Sentinel for duplicate-key allocations: the server returns rkey=0, addr=0

@@ -135,6 +135,28 @@ bool launch_transform_blocks(int dev, Stream s, PageCodec codec, PageDir dir,
 // loop iteration (four lanes per group).
 constexpr int kMxfp4GroupsPerIter = 64;
 
+// --- sliced reads -------------------------------------------------------------
+// Load direction only (core/page_codec.h, PageSlice; docs/design.md, "sliced
+// reads"): from each stored block take slice.n pieces of slice.piece_bytes
+// LOGICAL bytes, piece p at logical byte slice.offset + p * slice.stride of
+// the page the block was written with, and write their concatenation, the
+// sliced page, to the client page, itself split into seg.n segments when
+// seg.n > 1. Descriptors are what they are elsewhere (stored block base,
+// client page base, device-visible); the geometry rides in the kernel
+// arguments. One kernel per stored format: plain 16 B/lane, plain byte-wise
+// (chosen when the client pointers, offset, piece, stride or client stride are
+// not all 16-byte multiples), fp8 -> bf16 with block i's scale in
+// dev_scales[i], mxfp4 -> bf16 (dev_scales ignored). aligned16 says that every
+// descriptor pointer is 16-byte aligned (the CALLER checks). Returns false
+// before any launch for an illegal geometry (slice_legal), a transforming
+// codec without aligned16, or a grid that does not fit.
+bool launch_load_sliced(int dev, Stream s, PageCodec codec, const uint64_t* dev_src_ptrs,
+                        const uint64_t* dev_dst_ptrs, const float* dev_scales, int n_blocks,
+                        PageSlice slice, PageSegments seg, bool aligned16);
+// Workgroup size of the four sliced kernels, public so that tests compute the
+// edges of the lane mapping from it.
+constexpr int kSliceThreads = 512;
+
 // --- block fingerprint ------------------------------------------------------
 // 64-bit position-salted fingerprint per block -> out_hashes[i] (device mem).
 bool launch_hash_blocks(int dev, Stream s, const uint64_t* dev_ptrs, int n_blocks,

@@ -878,6 +878,209 @@ bool launch_transform_blocks(int dev, Stream stream, PageCodec codec, PageDir di
     return true;
 }
 
+// --- sliced reads --------------------------------------------------------------
+// From each stored block take n_pieces pieces, piece p at LOGICAL byte
+// offset + p * stride of the written page, and write their concatenation into
+// the client page (gpu.h, docs/design.md "sliced reads"). Real pieces are
+// small (one head group: 256 B to 2 KiB), so a workgroup per piece would idle
+// most of its lanes. Instead L, the smallest power of two >= units per piece
+// (capped at the workgroup), lanes share a piece and a workgroup covers
+// blockDim.x / L pieces per step: threadIdx.x >> lane_shift picks the piece of
+// the step, threadIdx.x & (L - 1) the unit lane, which strides by L inside the
+// piece. Everything in the unit loop is a shift, a mask or an add. The
+// workgroup is (block, chunk): chunk c of a block takes the steps c, c +
+// chunks, ...; the chunk count meets the same ~4096-workgroup target as
+// copy_chunks_per_block, and block b's descriptor pair is read once through
+// LDS as in block_chunk_descs. Per piece, once: its logical byte inside the
+// page (each kernel maps that to its stored address) and its client address
+// dst + (p / pieces_per_seg) * seg_stride + (p % pieces_per_seg) * piece_bytes.
+struct SliceArgs {
+    uint32_t n_pieces;
+    uint32_t chunks;          // workgroups per block
+    uint32_t lane_shift;      // log2(L)
+    uint32_t pieces_per_seg;  // n_pieces / client segments
+    uint64_t units;           // per piece, in the kernel's unit
+    uint64_t offset;          // logical bytes, as in PageSlice
+    uint64_t stride;
+    uint64_t piece_bytes;
+    uint64_t seg_stride;      // client bytes from one segment to the next
+    uint64_t page_bytes;      // logical size of the written page
+};
+
+// Walks the workgroup's pieces; move(b, src, logical_byte, client_addr, lane,
+// L) runs one piece's unit loop (b for the per-block scale).
+template <typename Move>
+__device__ __forceinline__ void slice_for_each_piece(const uint64_t* __restrict__ src_ptrs,
+                                                     const uint64_t* __restrict__ dst_ptrs,
+                                                     const SliceArgs& a, Move move) {
+    uint32_t b = blockIdx.x / a.chunks;
+    uint32_t chunk = blockIdx.x - b * a.chunks;
+    __shared__ uint64_t lds[2];
+    if (threadIdx.x == 0) {
+        lds[0] = src_ptrs[b];
+        lds[1] = dst_ptrs[b];
+    }
+    __syncthreads();
+    const uint64_t src = lds[0], dst = lds[1];
+    const uint32_t L = 1u << a.lane_shift;
+    const uint32_t per_step = blockDim.x >> a.lane_shift;
+    const uint32_t lane = threadIdx.x & (L - 1);
+    for (uint32_t p = chunk * per_step + (threadIdx.x >> a.lane_shift); p < a.n_pieces;
+         p += a.chunks * per_step) {
+        uint32_t sg = p / a.pieces_per_seg;
+        uint32_t r = p - sg * a.pieces_per_seg;
+        move(b, src, a.offset + p * a.stride, dst + sg * a.seg_stride + r * a.piece_bytes, lane,
+             L);
+    }
+}
+
+// plain: stored byte = logical byte. 16 bytes per lane; pointers, offset,
+// piece, stride and client stride are all 16-byte multiples (the launcher
+// picks the byte kernel otherwise).
+__global__ void load_sliced_vec_kernel(const uint64_t* __restrict__ src_ptrs,
+                                       const uint64_t* __restrict__ dst_ptrs, SliceArgs a) {
+    slice_for_each_piece(src_ptrs, dst_ptrs, a,
+                         [&](uint32_t, uint64_t src, uint64_t lbyte, uint64_t d, uint32_t lane,
+                             uint32_t L) {
+                             const uint4* s4 = reinterpret_cast<const uint4*>(src + lbyte);
+                             uint4* d4 = reinterpret_cast<uint4*>(d);
+                             for (uint64_t u = lane; u < a.units; u += L) d4[u] = s4[u];
+                         });
+}
+
+__global__ void load_sliced_byte_kernel(const uint64_t* __restrict__ src_ptrs,
+                                        const uint64_t* __restrict__ dst_ptrs, SliceArgs a) {
+    slice_for_each_piece(src_ptrs, dst_ptrs, a,
+                         [&](uint32_t, uint64_t src, uint64_t lbyte, uint64_t d, uint32_t lane,
+                             uint32_t L) {
+                             const uint8_t* s1 = reinterpret_cast<const uint8_t*>(src + lbyte);
+                             uint8_t* d1 = reinterpret_cast<uint8_t*>(d);
+                             for (uint64_t u = lane; u < a.units; u += L) d1[u] = s1[u];
+                         });
+}
+
+// fp8: stored byte = logical ELEMENT index, so a piece's codes start at
+// lbyte / 2: 8-byte aligned (offset and stride are multiples of 16 logical
+// bytes), not 16. A lane loads 8 codes (uint2) and stores 8 bf16 (uint4). The
+// block's one scale is scales[b]; nothing needs a page-wide pass, so the
+// mapping is the copy's, not one workgroup per page.
+__global__ void load_sliced_fp8_bf16_kernel(const uint64_t* __restrict__ src_ptrs,
+                                            const uint64_t* __restrict__ dst_ptrs,
+                                            const float* __restrict__ scales, SliceArgs a) {
+    slice_for_each_piece(
+        src_ptrs, dst_ptrs, a,
+        [&](uint32_t b, uint64_t src, uint64_t lbyte, uint64_t d, uint32_t lane, uint32_t L) {
+            const float scale = scales[b];
+            const uint2* s2 = reinterpret_cast<const uint2*>(src + lbyte / kPageElemBytes);
+            uint4* d4 = reinterpret_cast<uint4*>(d);
+            for (uint64_t u = lane; u < a.units; u += L) {
+                uint2 pk = s2[u];
+                const uint8_t* c = reinterpret_cast<const uint8_t*>(&pk);
+                uint16_t out[8];
+#pragma unroll
+                for (int i = 0; i < 8; i++) out[i] = fp8::decode_to_bf16(c[i], scale);
+                d4[u] = *reinterpret_cast<const uint4*>(out);
+            }
+        });
+}
+
+// mxfp4: a lane's 8 codes are the 4 bytes at page-global unit
+// g = lbyte / 16 + u, its scale byte sits behind all codes at
+// page_elems / 2 + (g >> 2), page_elems being the WRITTEN page's. Decoding is
+// lane-local: the quad shuffles exist only in the quantizer, so no quad of
+// lanes has to run together here and any lane count per piece is fine. (A
+// piece is whole 32-element groups, so u and g agree in their low two bits.)
+__global__ void load_sliced_mxfp4_bf16_kernel(const uint64_t* __restrict__ src_ptrs,
+                                              const uint64_t* __restrict__ dst_ptrs,
+                                              SliceArgs a) {
+    slice_for_each_piece(
+        src_ptrs, dst_ptrs, a,
+        [&](uint32_t, uint64_t src, uint64_t lbyte, uint64_t d, uint32_t lane, uint32_t L) {
+            const uint64_t g0 = lbyte / 16;  // 8 elements of 2 bytes per unit
+            const uint32_t* codes = reinterpret_cast<const uint32_t*>(src) + g0;
+            const uint8_t* sc =
+                reinterpret_cast<const uint8_t*>(src) + a.page_bytes / kPageElemBytes / 2;
+            uint4* d4 = reinterpret_cast<uint4*>(d);
+            for (uint64_t u = lane; u < a.units; u += L) {
+                uint32_t pk = codes[u];
+                uint8_t E = sc[(g0 + u) >> 2];
+                uint16_t out[8];
+#pragma unroll
+                for (int i = 0; i < 8; i++)
+                    out[i] = mxfp4::decode(static_cast<uint8_t>((pk >> (4 * i)) & 0xfu), E);
+                d4[u] = *reinterpret_cast<const uint4*>(out);
+            }
+        });
+}
+
+bool launch_load_sliced(int dev, Stream stream, PageCodec codec, const uint64_t* dev_src_ptrs,
+                        const uint64_t* dev_dst_ptrs, const float* dev_scales, int n_blocks,
+                        PageSlice slice, PageSegments seg, bool aligned16) {
+    if (n_blocks <= 0) return true;
+    if (!slice_legal(codec, slice, seg)) {
+        snprintf(g_err, sizeof(g_err), "launch_load_sliced: illegal page slice");
+        return false;
+    }
+    const bool transforms = page_codec_transforms(codec);
+    if (transforms && !aligned16) {
+        snprintf(g_err, sizeof(g_err), "launch_load_sliced: %s needs 16-byte-aligned pointers",
+                 page_codec_info(codec).name);
+        return false;
+    }
+    if (page_codec_info(codec).page_scale && !dev_scales) return false;
+    const bool many = slice.n > 1, segmented = seg.n > 1;
+    // The transforming kernels' unit is 8 elements: 16 logical bytes.
+    const bool vec = transforms ||
+                     (aligned16 && slice.offset % 16 == 0 && slice.piece_bytes % 16 == 0 &&
+                      (!many || slice.stride % 16 == 0) &&
+                      (!segmented || seg.stride_bytes % 16 == 0));
+    SliceArgs a;
+    a.n_pieces = slice.n;
+    a.units = vec ? slice.piece_bytes / 16 : slice.piece_bytes;
+    a.lane_shift = 0;
+    while ((1ull << a.lane_shift) < a.units && (1 << a.lane_shift) < kSliceThreads)
+        a.lane_shift++;
+    const uint32_t per_step = static_cast<uint32_t>(kSliceThreads) >> a.lane_shift;
+    const uint64_t steps = (slice.n + per_step - 1) / per_step;
+    a.chunks = copy_chunks_per_block(steps, n_blocks, 1);
+    a.pieces_per_seg = slice.n / seg.n;
+    a.offset = slice.offset;
+    a.stride = many ? slice.stride : 0;
+    a.piece_bytes = slice.piece_bytes;
+    a.seg_stride = segmented ? seg.stride_bytes : 0;
+    a.page_bytes = slice.page_bytes;
+    const uint64_t g = static_cast<uint64_t>(n_blocks) * a.chunks;
+    if (g > 0x7fffffffull) {
+        snprintf(g_err, sizeof(g_err), "launch_load_sliced: grid does not fit");
+        return false;
+    }
+    HIP_OK(hipSetDevice(dev));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const dim3 grid(static_cast<uint32_t>(g)), block(kSliceThreads);
+    switch (codec) {
+        case PageCodec::kNone:
+            if (vec)
+                hipLaunchKernelGGL(load_sliced_vec_kernel, grid, block, 0, s, dev_src_ptrs,
+                                   dev_dst_ptrs, a);
+            else
+                hipLaunchKernelGGL(load_sliced_byte_kernel, grid, block, 0, s, dev_src_ptrs,
+                                   dev_dst_ptrs, a);
+            break;
+        case PageCodec::kFp8:
+            hipLaunchKernelGGL(load_sliced_fp8_bf16_kernel, grid, block, 0, s, dev_src_ptrs,
+                               dev_dst_ptrs, dev_scales, a);
+            break;
+        case PageCodec::kMxfp4:
+            hipLaunchKernelGGL(load_sliced_mxfp4_bf16_kernel, grid, block, 0, s, dev_src_ptrs,
+                               dev_dst_ptrs, a);
+            break;
+        default:
+            return false;
+    }
+    HIP_OK(hipGetLastError());
+    return true;
+}
+
 // --- fingerprint -----------------------------------------------------------
 // Position-salted 64-bit mix (splitmix64 finalizer); XOR-combined across a
 // block so the reduction is order-free, deterministic, and parallel.

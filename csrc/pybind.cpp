@@ -328,6 +328,57 @@ std::vector<float> transform_blocks_seg_py(const char* what, int codec_id, PageD
     return scales;
 }
 
+// ---- sliced reads (docs/design.md, "sliced reads") ---------------------------
+// A slice from Python: None, or (n_pieces, page, offset, piece, stride) in
+// units of `unit` bytes (the tensor's element size; 1 for the byte-level
+// debug entries).
+PageSlice slice_from_py(const char* what, const py::object& o, uint64_t unit) {
+    PageSlice sl;
+    if (o.is_none()) return sl;
+    py::tuple t = o.cast<py::tuple>();
+    if (t.size() != 5)
+        throw std::invalid_argument(std::string(what) +
+                                    ": a slice is (n_pieces, page, offset, piece, stride)");
+    sl.n = t[0].cast<uint32_t>();
+    sl.page_bytes = t[1].cast<uint64_t>() * unit;
+    sl.offset = t[2].cast<uint64_t>() * unit;
+    sl.piece_bytes = t[3].cast<uint64_t>() * unit;
+    sl.stride = t[4].cast<uint64_t>() * unit;
+    return sl;
+}
+
+// The sliced-load launcher, called directly: stored blocks -> client pages.
+// Returns what the launcher returns, so a refusal is False, not an exception;
+// aligned16 is computed from the pointers as Shard::submit_copy does.
+bool load_sliced_py(int codec_id, const std::vector<uint64_t>& stored,
+                    const std::vector<uint64_t>& client, const std::vector<float>& scales,
+                    const py::object& slice, uint32_t n_segments, uint64_t segment_stride,
+                    int device) {
+    const char* what = "_dbg_load_sliced";
+    const PageCodec codec = codec_from_id(what, codec_id);
+    const PageSlice sl = slice_from_py(what, slice, 1);
+    require_gpu_and_pairs(what, stored, client);
+    size_t n = stored.size();
+    if (page_codec_info(codec).page_scale && scales.size() != n)
+        throw std::invalid_argument(std::string(what) + ": one scale per block");
+    if (n == 0) return true;
+    py::gil_scoped_release rel;
+    Pinned<uint64_t> h_src(n), h_dst(n);
+    Pinned<float> h_scale(n);
+    memcpy(h_src.p, stored.data(), n * 8);
+    memcpy(h_dst.p, client.data(), n * 8);
+    memcpy(h_scale.p, scales.data(), std::min(scales.size(), n) * sizeof(float));
+    ScopedStream st(device);
+    bool ok = gpu::launch_load_sliced(device, st.s, codec, h_src.p, h_dst.p, h_scale.p,
+                                      static_cast<int>(n), sl,
+                                      PageSegments{n_segments, segment_stride},
+                                      all_aligned16(stored, client));
+    // Always drain the stream before the pinned descriptors go away.
+    if (!gpu::stream_sync(st.s))
+        throw std::runtime_error(std::string(what) + " failed: " + gpu::last_error());
+    return ok;
+}
+
 // (codec id, stored bytes) of a request with these flags and this logical
 // page size, by the codec table alone (host-only).
 std::pair<int, size_t> page_codec_py(uint32_t flags, size_t page_bytes) {
@@ -396,10 +447,14 @@ struct ShardRun {
     }
 };
 
-py::tuple shard_run_py(int device, int n_streams, int slots_per_stream,
-                       size_t max_descs_per_slot, const py::list& copy_jobs,
-                       const py::list& fabric_jobs, int n_threads, double timeout_s) {
-    const char* what = "_dbg_shard_run";
+// slices (null for _dbg_shard_run): one entry per copy job, None or the job's
+// slice in bytes as slice_from_py takes it.
+py::tuple shard_run_impl(const char* what, int device, int n_streams, int slots_per_stream,
+                         size_t max_descs_per_slot, const py::list& copy_jobs,
+                         const py::list& fabric_jobs, int n_threads, double timeout_s,
+                         const py::list* slices) {
+    if (slices && slices->size() != copy_jobs.size())
+        throw std::invalid_argument(std::string(what) + ": one slice (or None) per copy job");
     if (device < -1) throw std::invalid_argument(std::string(what) + ": device is -1 or an ordinal");
     if (device >= 0 && (!gpu::available() || device >= gpu::device_count()))
         throw std::runtime_error(std::string(what) + ": no such GPU available");
@@ -429,6 +484,7 @@ py::tuple shard_run_py(int device, int n_streams, int slots_per_stream,
         if (!t[7].is_none())
             j.scales = std::make_shared<std::vector<float>>(t[7].cast<std::vector<float>>());
         j.scales_off = t[8].cast<size_t>();
+        if (slices) j.slice = slice_from_py(what, (*slices)[i], 1);
         j.done = [run, i](bool ok) { run->on_done(i, ok); };
         st->scales.push_back(j.scales);
         st->copy_jobs.push_back(std::move(j));
@@ -544,6 +600,14 @@ py::tuple shard_run_py(int device, int n_streams, int slots_per_stream,
     return py::make_tuple(copy_out, fabric_out);
 }
 
+py::tuple shard_run_py(int device, int n_streams, int slots_per_stream,
+                       size_t max_descs_per_slot, const py::list& copy_jobs,
+                       const py::list& fabric_jobs, int n_threads, double timeout_s) {
+    return shard_run_impl("_dbg_shard_run", device, n_streams, slots_per_stream,
+                          max_descs_per_slot, copy_jobs, fabric_jobs, n_threads, timeout_s,
+                          nullptr);
+}
+
 // Shard::completion_loop's search (server/completed_prefix.h) over a modelled
 // queue: has_slot[i] says whether task i is real; at the k-th question
 // fired_at_query[k] (its last value from then on) real tasks, in FIFO order,
@@ -648,7 +712,11 @@ PYBIND11_MODULE(_native, m) {
             [](ClientConn& c, const std::string& op, py::list keys, py::buffer offsets,
                uint64_t element_size, int block_size, uintptr_t ptr, int device,
                bool sync_response, uint32_t extra_flags, uint32_t n_segments,
-               uint64_t segment_stride) {
+               uint64_t segment_stride, const py::object& page_slice) {
+                // page_slice: None or (n_pieces, page, offset, piece, stride)
+                // in elements; reads only (the client refuses it on 'W').
+                const PackedLocalSliceExt sl =
+                    slice_to_wire(slice_from_py("rw_local", page_slice, element_size));
                 // Build the NUL-joined key blob and byte offsets in C++ —
                 // no Python-side join/numpy work on the hot path.
                 py::buffer_info ob = offsets.request();
@@ -672,18 +740,23 @@ PYBIND11_MODULE(_native, m) {
                 return c.rw_local_packed(op.empty() ? 'W' : op[0], blob.data(), blob.size(),
                                          byte_offs.data(), n, block_size, ptr, device,
                                          sync_response, nullptr, extra_flags, n_segments,
-                                         segment_stride * element_size);
+                                         segment_stride * element_size, &sl);
             },
             py::arg("op"), py::arg("keys"), py::arg("offsets"), py::arg("element_size"),
             py::arg("block_size"), py::arg("ptr"), py::arg("device"),
             py::arg("sync_response") = false, py::arg("extra_flags") = 0,
-            py::arg("n_segments") = 1, py::arg("segment_stride") = 0)
+            py::arg("n_segments") = 1, py::arg("segment_stride") = 0,
+            py::arg("page_slice") = py::none())
         .def(
             "rw_local_blob",
             [](ClientConn& c, const std::string& op, py::buffer blob, py::buffer offsets,
                uint64_t element_size, int block_size, uintptr_t ptr, int device,
                bool sync_response, uint32_t extra_flags, uint32_t n_segments,
-               uint64_t segment_stride) {
+               uint64_t segment_stride, const py::object& page_slice) {
+                // page_slice: None or (n_pieces, page, offset, piece, stride)
+                // in elements; reads only (the client refuses it on 'W').
+                const PackedLocalSliceExt sl =
+                    slice_to_wire(slice_from_py("rw_local", page_slice, element_size));
                 // Zero-pack fast path: keys as one NUL-separated bytes blob
                 // (engines cache the serialized page-key chain; re-joining
                 // 2k Python strings costs ~30 µs per request otherwise).
@@ -700,17 +773,20 @@ PYBIND11_MODULE(_native, m) {
                 return c.rw_local_packed(op.empty() ? 'W' : op[0], bp, blen, byte_offs.data(),
                                          n, block_size, ptr, device, sync_response, nullptr,
                                          extra_flags, n_segments,
-                                         segment_stride * element_size);
+                                         segment_stride * element_size, &sl);
             },
             py::arg("op"), py::arg("blob"), py::arg("offsets"), py::arg("element_size"),
             py::arg("block_size"), py::arg("ptr"), py::arg("device"),
             py::arg("sync_response") = false, py::arg("extra_flags") = 0,
-            py::arg("n_segments") = 1, py::arg("segment_stride") = 0)
+            py::arg("n_segments") = 1, py::arg("segment_stride") = 0,
+            py::arg("page_slice") = py::none())
         .def(
             "rw_local_blob_async",
             [](ClientConn& c, const std::string& op, py::buffer blob, py::buffer offsets,
                uint64_t element_size, int block_size, uintptr_t ptr, int device,
-               uint32_t n_segments, uint64_t segment_stride) {
+               uint32_t n_segments, uint64_t segment_stride, const py::object& page_slice) {
+                const PackedLocalSliceExt sl =
+                    slice_to_wire(slice_from_py("rw_local", page_slice, element_size));
                 // Ticketed form: push the (sync-response) op and return a
                 // ticket to pass to wait_local_ticket — the engine overlaps
                 // its own work with the copy. Ticket 0 = already complete
@@ -731,13 +807,14 @@ PYBIND11_MODULE(_native, m) {
                     ret = c.rw_local_packed(op.empty() ? 'R' : op[0], bp, blen,
                                             byte_offs.data(), n, block_size, ptr, device,
                                             /*sync_response=*/true, &ticket, 0, n_segments,
-                                            segment_stride * element_size);
+                                            segment_stride * element_size, &sl);
                 }
                 return py::make_tuple(ret, ticket);
             },
             py::arg("op"), py::arg("blob"), py::arg("offsets"), py::arg("element_size"),
             py::arg("block_size"), py::arg("ptr"), py::arg("device"),
-            py::arg("n_segments") = 1, py::arg("segment_stride") = 0)
+            py::arg("n_segments") = 1, py::arg("segment_stride") = 0,
+            py::arg("page_slice") = py::none())
         .def("wait_local_ticket", &ClientConn::wait_local_ticket,
              py::call_guard<py::gil_scoped_release>())
         .def("sync_local", &ClientConn::sync_local, py::call_guard<py::gil_scoped_release>())
@@ -925,6 +1002,39 @@ PYBIND11_MODULE(_native, m) {
           py::arg("codec"), py::arg("page_bytes"), py::arg("n_segments"),
           py::arg("stride_bytes"));
     m.attr("_MAX_PAGE_SEGMENTS") = kMaxPageSegments;
+    // The slice-geometry predicate; the slice is (n_pieces, page_bytes, offset,
+    // piece_bytes, stride) in bytes, the client segments as above.
+    m.def("_dbg_slice_legal",
+          [](int codec, const py::object& slice, uint32_t n_segments, uint64_t stride_bytes) {
+              if (slice.is_none())
+                  throw std::invalid_argument("_dbg_slice_legal: a slice is a tuple of 5");
+              return slice_legal(codec_from_id("_dbg_slice_legal", codec),
+                                 slice_from_py("_dbg_slice_legal", slice, 1),
+                                 PageSegments{n_segments, stride_bytes});
+          },
+          py::arg("codec"), py::arg("slice"), py::arg("n_segments") = 1,
+          py::arg("stride_bytes") = 0);
+    m.attr("_MAX_SLICE_PIECES") = kMaxSlicePieces;
+    m.attr("_SLICE_THREADS") = gpu::kSliceThreads;
+    // The sliced-load launcher (gpu.h, launch_load_sliced), called directly:
+    // codec id, stored block pointers, client page pointers, one scale per
+    // block for fp8 (else ignored), the slice in bytes, the client segments.
+    m.def("_dbg_load_sliced", &load_sliced_py, py::arg("codec"), py::arg("stored_ptrs"),
+          py::arg("client_ptrs"), py::arg("scales"), py::arg("slice"),
+          py::arg("n_segments") = 1, py::arg("segment_stride") = 0, py::arg("device") = 0);
+    // _dbg_shard_run's copy jobs, each with a slice (or None) from `slices`.
+    m.def("_dbg_shard_run_sliced",
+          [](int device, int n_streams, int slots_per_stream, size_t max_descs_per_slot,
+             const py::list& copy_jobs, const py::list& slices, int n_threads,
+             double timeout_s) -> py::object {
+              py::tuple out = shard_run_impl("_dbg_shard_run_sliced", device, n_streams,
+                                             slots_per_stream, max_descs_per_slot, copy_jobs,
+                                             py::list(), n_threads, timeout_s, &slices);
+              return out[0];
+          },
+          py::arg("device"), py::arg("n_streams"), py::arg("slots_per_stream"),
+          py::arg("max_descs_per_slot"), py::arg("copy_jobs"), py::arg("slices"),
+          py::arg("n_threads"), py::arg("timeout_s"));
     // Jobs through a real Shard at small limits. A copy job is (src_ptrs,
     // dst_ptrs, bytes_per_block, codec_id, store, n_segments, segment_stride,
     // scales or None, scales_off), a fabric job (is_put, host buffer,
@@ -939,12 +1049,15 @@ PYBIND11_MODULE(_native, m) {
     m.def("_dbg_completed_prefix", &completed_prefix_py, py::arg("has_slot"),
           py::arg("fired_at_query"));
     // Packed fast-path framing (core/protocol.h), with and without the
-    // segment extension. op is "w" or "r"; offsets are in bytes.
+    // segment and slice extensions. op is "w" or "r"; offsets and the slice
+    // (n_pieces, page_bytes, offset, piece_bytes, stride) are in bytes.
     m.def("_dbg_build_packed_local",
           [](int device, int pid, uint64_t base_ptr, uint64_t base_offset, uint32_t block_size,
              uint32_t flags, uint32_t alloc_mb, py::bytes ipc,
              const std::vector<uint64_t>& offsets, const std::vector<std::string>& keys,
-             uint32_t n_segments, uint64_t segment_stride) {
+             uint32_t n_segments, uint64_t segment_stride, const py::object& slice) {
+              const PackedLocalSliceExt sl =
+                  slice_to_wire(slice_from_py("_dbg_build_packed_local", slice, 1));
               std::string ipc_s = ipc;
               if (ipc_s.size() != 64)
                   throw std::invalid_argument("_dbg_build_packed_local: ipc is 64 bytes");
@@ -966,13 +1079,13 @@ PYBIND11_MODULE(_native, m) {
                   blob.append(keys[i]);
               }
               auto v = build_packed_local(h, n_segments, segment_stride, offsets.data(),
-                                          blob.data(), blob.size());
+                                          blob.data(), blob.size(), &sl);
               return py::bytes(reinterpret_cast<const char*>(v.data()), v.size());
           },
           py::arg("device"), py::arg("pid"), py::arg("base_ptr"), py::arg("base_offset"),
           py::arg("block_size"), py::arg("flags"), py::arg("alloc_mb"), py::arg("ipc"),
           py::arg("offsets"), py::arg("keys"), py::arg("n_segments") = 1,
-          py::arg("segment_stride") = 0);
+          py::arg("segment_stride") = 0, py::arg("slice") = py::none());
     m.def("_dbg_parse_packed_local", [](const std::string& op, py::bytes data) {
         std::string s = data;
         PackedLocalReq r;
@@ -990,6 +1103,12 @@ PYBIND11_MODULE(_native, m) {
         d["alloc_mb"] = r.hdr.rsvd;
         d["n_segments"] = r.n_segments;
         d["segment_stride"] = r.segment_stride;
+        // None, or (n_pieces, page_bytes, offset, piece_bytes, stride)
+        if (r.slice.n_pieces)
+            d["slice"] = py::make_tuple(r.slice.n_pieces, r.slice.page_bytes, r.slice.offset,
+                                        r.slice.piece_bytes, r.slice.stride);
+        else
+            d["slice"] = py::none();
         py::list offs, keys;
         for (auto& [key, off] : r.blocks) {
             offs.append(off);

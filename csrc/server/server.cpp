@@ -540,6 +540,7 @@ bool parse_packed_local(char op, const uint8_t* body, size_t body_len, Server::L
     v->alloc_mb = h.rsvd;
     v->n_segments = req.n_segments;
     v->segment_stride = req.segment_stride;
+    v->slice = slice_from_wire(req.slice);
     v->ipc = body + offsetof(PackedLocalHdr, ipc);
     v->ipc_len = 64;
     v->blocks = std::move(req.blocks);
@@ -955,6 +956,14 @@ void Server::op_local_read(Conn* c, const LocalView& msg, const ReqCtx& ctx) {
     // stored_matches.
     if (!segments_legal(PageCodec::kNone, page, msg.n_segments, msg.segment_stride))
         return reply_local(c, ctx, INVALID_REQ);
+    // Sliced read: `page` is the sliced page (what the client receives); the
+    // stored pages are slice.page_bytes. Plain rules here too, as in the
+    // parser; the sweep checks every entry against its own codec.
+    const bool sliced = slice_is_set(msg.slice);
+    const PageSegments client_seg{msg.n_segments, msg.segment_stride};
+    if (sliced && (!slice_legal(PageCodec::kNone, msg.slice, client_seg) ||
+                   page != msg.slice.n * msg.slice.piece_bytes))
+        return reply_local(c, ctx, INVALID_REQ);
 
     auto tr0 = Clock::now();
     // Group blocks by the shard whose GPU EXECUTES the copy. For same-GPU
@@ -1003,12 +1012,25 @@ void Server::op_local_read(Conn* c, const LocalView& msg, const ReqCtx& ctx) {
             }
             BlockEntry* e = v->get();
             e->last_access.store(read_tick, std::memory_order_relaxed);
-            // Compressed entries: the page must be the written size, and
-            // the dequantize kernels store 16 bytes per lane into the client.
-            if (page_codec_transforms(e->codec) &&
-                (!stored_matches(e->codec, e->size, page) ||
-                 reinterpret_cast<uintptr_t>(client_ptr + b.second) % 16 != 0 ||
-                 !segments_legal(e->codec, page, msg.n_segments, msg.segment_stride))) {
+            if (sliced) {
+                // Every entry, plain ones included, must hold a page of the
+                // size the slice was cut for, and the geometry must be legal
+                // for the entry's own codec; a compressed entry needs the
+                // 16-byte-aligned client address as below.
+                if (!stored_matches(e->codec, e->size, msg.slice.page_bytes) ||
+                    !slice_legal(e->codec, msg.slice, client_seg) ||
+                    (page_codec_transforms(e->codec) &&
+                     reinterpret_cast<uintptr_t>(client_ptr + b.second) % 16 != 0)) {
+                    err = INVALID_REQ;
+                    return false;
+                }
+            } else if (page_codec_transforms(e->codec) &&
+                       // Compressed entries: the page must be the written size,
+                       // and the dequantize kernels store 16 bytes per lane
+                       // into the client.
+                       (!stored_matches(e->codec, e->size, page) ||
+                        reinterpret_cast<uintptr_t>(client_ptr + b.second) % 16 != 0 ||
+                        !segments_legal(e->codec, page, msg.n_segments, msg.segment_stride))) {
                 err = INVALID_REQ;
                 return false;
             }
@@ -1024,6 +1046,7 @@ void Server::op_local_read(Conn* c, const LocalView& msg, const ReqCtx& ctx) {
                     it->second.dir = PageDir::kLoad;
                     it->second.n_segments = msg.n_segments;
                     it->second.segment_stride = msg.segment_stride;
+                    it->second.slice = msg.slice;
                     if (page_codec_info(e->codec).page_scale)
                         it->second.scales = std::make_shared<std::vector<float>>();
                 }

@@ -146,6 +146,9 @@ class Server {
         // of client memory segment_stride bytes apart; 1 = contiguous.
         uint32_t n_segments = 1;
         uint64_t segment_stride = 0;
+        // Sliced reads (OP_R_FAST only): slice.n != 0 asks for strided pieces
+        // of every stored page; block_size is then the sliced page.
+        PageSlice slice;
         const uint8_t* ipc = nullptr;
         size_t ipc_len = 0;
         std::vector<std::pair<std::string_view, uint64_t>> blocks;

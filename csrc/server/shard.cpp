@@ -225,6 +225,11 @@ bool Shard::submit_copy(CopyJob&& job) {
         return false;
     const bool segmented = job.n_segments > 1;
     const PageSegments seg{job.n_segments, segmented ? job.segment_stride : 0};
+    // A slice is a read-side geometry, and the job's page is the sliced page.
+    const bool sliced = slice_is_set(job.slice);
+    if (sliced && (job.dir != PageDir::kLoad || !slice_legal(job.codec, job.slice, seg) ||
+                   job.bytes_per_block != job.slice.n * job.slice.piece_bytes))
+        return false;
     // A codec with a per-page scale needs one scale slot per block.
     const bool page_scale = page_codec_info(job.codec).page_scale;
     if (page_scale && (!job.scales || job.scales->size() < job.scales_off + n)) return false;
@@ -246,6 +251,7 @@ bool Shard::submit_copy(CopyJob&& job) {
             sub.dir = job.dir;
             sub.n_segments = job.n_segments;
             sub.segment_stride = job.segment_stride;
+            sub.slice = job.slice;
             sub.scales = job.scales;
             sub.scales_off = job.scales_off + off;
             sub.src.assign(job.src.begin() + static_cast<long>(off),
@@ -269,6 +275,19 @@ bool Shard::submit_copy(CopyJob&& job) {
         // CPU shard: copies run inline on the caller (loop) thread.
         // A segmented page: the client side steps by the stride, the pool
         // side by the segment.
+        if (sliced) {
+            // The sliced page's pieces, in order, fill the client's segments.
+            const PageSlice& sl = job.slice;
+            const uint32_t per_seg = sl.n / seg.n;
+            for (size_t i = 0; i < n; i++)
+                for (uint32_t p = 0; p < sl.n; p++)
+                    memcpy(reinterpret_cast<void*>(job.dst[i] + (p / per_seg) * seg.stride_bytes +
+                                                   (p % per_seg) * sl.piece_bytes),
+                           reinterpret_cast<const void*>(job.src[i] + sl.offset + p * sl.stride),
+                           sl.piece_bytes);
+            if (job.done) job.done(true);
+            return true;
+        }
         const size_t seg_bytes = job.bytes_per_block / seg.n;
         const uint64_t src_step = job.dir == PageDir::kStore ? seg.stride_bytes : seg_bytes;
         const uint64_t dst_step = job.dir == PageDir::kStore ? seg_bytes : seg.stride_bytes;
@@ -286,6 +305,11 @@ bool Shard::submit_copy(CopyJob&& job) {
     // size: both must keep the 16-byte alignment too.
     if (segmented)
         aligned = aligned && (job.bytes_per_block / seg.n) % 16 == 0 && seg.stride_bytes % 16 == 0;
+    // A slice's pieces start at offset + p * stride on the pool side and at
+    // multiples of the piece on the client side.
+    if (sliced)
+        aligned = aligned && job.slice.offset % 16 == 0 && job.slice.piece_bytes % 16 == 0 &&
+                  (job.slice.n == 1 || job.slice.stride % 16 == 0);
     if (aligned) {
         for (size_t i = 0; i < n && aligned; i++)
             aligned = (job.src[i] % 16 == 0) && (job.dst[i] % 16 == 0);
@@ -326,8 +350,8 @@ bool Shard::submit_copy(CopyJob&& job) {
     StreamCtx& sc = streams_[pick];
 
     // Small aligned batches: descriptors ride in the kernel arguments.
-    // (Segmented jobs always use the pinned-descriptor kernels.)
-    if (aligned && n <= 16 && !transforms && !segmented) {
+    // (Segmented and sliced jobs always use the pinned-descriptor kernels.)
+    if (aligned && n <= 16 && !transforms && !segmented && !sliced) {
         Slot* slot = acquire_slot(sc);
         if (!slot) return false;
         bool ok = gpu::set_device(opt_.device) &&
@@ -364,7 +388,16 @@ bool Shard::submit_copy(CopyJob&& job) {
         // profiles/rocprof_bench_r02.txt).
         const uint64_t* dsrc = slot->h_src;
         const uint64_t* ddst = slot->h_dst;
-        if (!transforms) {
+        if (sliced) {
+            // One launcher for every codec; fp8's scales ride in h_scale as
+            // for the whole-page dequantize below.
+            if (page_scale)
+                memcpy(slot->h_scale, job.scales->data() + job.scales_off + off,
+                       take * sizeof(float));
+            ok = ok && gpu::launch_load_sliced(opt_.device, sc.stream, job.codec, dsrc, ddst,
+                                               slot->h_scale, static_cast<int>(take), job.slice,
+                                               seg, aligned);
+        } else if (!transforms) {
             ok = ok && gpu::launch_copy_blocks(opt_.device, sc.stream, dsrc, ddst,
                                                static_cast<int>(take), job.bytes_per_block,
                                                aligned, seg, job.dir);

@@ -57,6 +57,12 @@ class Shard {
         // the pool side is contiguous. 1 = contiguous (stride ignored).
         uint32_t n_segments = 1;
         uint64_t segment_stride = 0;
+        // Sliced reads (core/page_codec.h): with slice.n != 0 the POOL side
+        // (src) gives slice.n strided pieces of the stored page and
+        // bytes_per_block is the sliced page, slice.n * slice.piece_bytes.
+        // kLoad only; segments apply to the sliced page. Such a job never
+        // takes the inline-argument path.
+        PageSlice slice;
         // Codecs with a per-page scale: block i's scale is
         // (*scales)[scales_off + i], written before done() by kStore and
         // read at submit by kLoad. Fan-out sub-jobs share the vector.

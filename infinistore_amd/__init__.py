@@ -7,6 +7,7 @@ extensions (fingerprint_blocks, get_server_stats, unregister_server).
 
 from .lib import (
     InfinityConnection,
+    PageSlice,
     DisableTorchCaching,
     ClientConfig,
     ServerConfig,
@@ -30,6 +31,7 @@ from .lib import (
 
 __all__ = [
     "InfinityConnection",
+    "PageSlice",
     "DisableTorchCaching",
     "register_server",
     "unregister_server",

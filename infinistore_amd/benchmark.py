@@ -54,6 +54,17 @@ def parse_args():
                    help="segmented pages (local-GPU path): lay each client "
                         "tensor out [N, n_pages, page/N] and move every page "
                         "as N segments a plane apart; 1 = contiguous pages")
+    p.add_argument("--slice", default=None, metavar="H0:H1/H",
+                   help="sliced reads (local-GPU path): view every page as "
+                        "[--slice-rows, H, head] and read only heads H0..H1 of "
+                        "each, into tightly packed sliced pages; the read rate "
+                        "then counts DELIVERED bytes")
+    p.add_argument("--slice-rows", type=int, default=32,
+                   help="rows (2 x block tokens) of the page view for --slice")
+    p.add_argument("--slice-baseline", action="store_true",
+                   help="with --slice: what a reader does without sliced reads, "
+                        "for comparison: read whole pages into a bounce buffer, "
+                        "then slice-copy the heads into place with torch")
     p.add_argument("--verify", action="store_true")
     p.add_argument("--json", action="store_true", help="print a JSON summary")
     p.add_argument("--spawn-server", action="store_true",
@@ -61,6 +72,26 @@ def parse_args():
     p.add_argument("--prealloc-size", type=int, default=8,
                    help="pool GB per shard for --spawn-server")
     return p.parse_args()
+
+
+def slice_geometry(args):
+    """(h0, h1, H, rows, head_elems) of --slice, or None. The page is viewed as
+    [rows, H, head_elems]."""
+    if not args.slice:
+        return None
+    try:
+        heads, total = args.slice.split("/")
+        h0, h1 = (int(v) for v in heads.split(":"))
+        H = int(total)
+    except ValueError:
+        raise SystemExit("--slice is H0:H1/H, e.g. 0:4/8")
+    es = 2 if args.quant else 4
+    page_elems = (args.block_size << 10) // es
+    rows = args.slice_rows
+    if not 0 <= h0 < h1 <= H or rows < 1 or page_elems % (rows * H):
+        raise SystemExit("--slice needs 0 <= H0 < H1 <= H and a page of "
+                         "--slice-rows x H whole heads")
+    return h0, h1, H, rows, page_elems // (rows * H)
 
 
 def make_conn(args, local):
@@ -132,6 +163,20 @@ def run_once(args, conn, local, device, bufs=None):
     nseg = args.segments
     seg_elems = page_elems // nseg
 
+    # --slice: the reads deliver heads h0..h1 of every page, packed, into outs.
+    sg = slice_geometry(args) if local else None
+    read_bytes = total_bytes
+    if sg:
+        h0, h1, n_heads, rows, head = sg
+        sliced_elems = rows * (h1 - h0) * head
+        read_bytes = n_blocks * sliced_elems * es
+        page_slice = lib.PageSlice(page_size=page_elems, offset=h0 * head,
+                                   piece=(h1 - h0) * head, stride=n_heads * head,
+                                   count=rows)
+        outs = [torch.zeros(d.numel() // page_elems * sliced_elems, dtype=d.dtype,
+                            device=d.device) for d in dsts]
+        torch.cuda.synchronize()
+
     def sub_of(i):  # block index -> (tensor index, element offset within it)
         return i // blocks_per_sub, (i % blocks_per_sub) * seg_elems
 
@@ -179,11 +224,25 @@ def run_once(args, conn, local, device, bufs=None):
                 ks = [keys[i] for i in range(c0, c1)]
                 offs = np.asarray([sub_of(i)[1] for i in range(c0, c1)],
                                   dtype=np.uint64)
+                if sg and not args.slice_baseline:
+                    offs = offs // np.uint64(page_elems) * np.uint64(sliced_elems)
+                    tickets.append(conn.read_pages_async(outs[t_idx], ks, offs,
+                                                         sliced_elems,
+                                                         page_slice=page_slice))
+                    continue
                 tickets.append(conn.read_pages_async(dsts[t_idx], ks, offs,
                                                      page_elems,
                                                      **geom(dsts[t_idx])))
         for tk in tickets:
             conn.wait_read(tk)
+        if sg and args.slice_baseline:
+            # the second pass a reader needs today: pick the heads out of the
+            # bounce buffer (dsts) into place
+            for d, o in zip(dsts, outs):
+                o.view(-1, rows, (h1 - h0) * head).copy_(
+                    d.view(-1, rows, n_heads, head)[:, :, h0:h1].reshape(
+                        -1, rows, (h1 - h0) * head))
+            torch.cuda.synchronize()
     else:
         for t_idx in range(len(dsts)):
             lo = t_idx * blocks_per_sub
@@ -194,7 +253,11 @@ def run_once(args, conn, local, device, bufs=None):
     conn.sync()
     r_time = time.perf_counter() - t0
 
-    if args.verify:
+    if args.verify and sg:
+        for a, o in zip(srcs, outs):
+            want = a.view(-1, rows, n_heads, head)[:, :, h0:h1].reshape(-1)
+            assert _close(want.cpu(), o.cpu(), args.quant), "verification failed (slice)"
+    elif args.verify:
         for a, b in zip(srcs, dsts):
             assert _close(a.cpu(), b.cpu(), args.quant), "verification failed"
         if nseg > 1:
@@ -208,7 +271,7 @@ def run_once(args, conn, local, device, bufs=None):
     except Exception:
         pass
 
-    return total_bytes / w_time / 1e6, total_bytes / r_time / 1e6
+    return total_bytes / w_time / 1e6, read_bytes / r_time / 1e6
 
 
 # Largest absolute error of a value in [0, 1) after a round trip through a
@@ -363,6 +426,10 @@ def main():
             raise SystemExit("--segments needs --local-gpu")
         if args.segments < 1 or ((args.block_size << 10) // es) % args.segments:
             raise SystemExit("--segments must divide the page's element count")
+    if args.slice:
+        if not args.local_gpu or args.segments != 1:
+            raise SystemExit("--slice needs --local-gpu and --segments 1")
+        slice_geometry(args)  # refuses a malformed option before anything starts
     if args.spawn_server and args.clients > 1:
         # Keys live until each iteration's trailing delete; size the pool
         # for all clients' live iterations plus slack, capped so the pool +

@@ -112,21 +112,25 @@ class PagedKVConnector:
     # -- decode side ----------------------------------------------------------
     def load_layer(self, layer: int, kv_out: torch.Tensor, page_keys: List[str],
                    page_offsets, page_elems: int, segments: int = 1,
-                   segment_stride: int = 0) -> bool:
+                   segment_stride: int = 0, page_slice=None) -> bool:
         """Gather this layer's cached pages into the engine's KV tensor.
         Returns False if any page is missing (caller falls back to compute).
-        segments / segment_stride: as in InfinityConnection.read_pages; a
+        segments / segment_stride / page_slice: as in
+        InfinityConnection.read_pages (page_elems is then the sliced page); a
         refused geometry raises ValueError."""
         keys = [self._key(layer, k) for k in page_keys]
         if segments != 1 and not self.local:
             raise ValueError("segmented pages use the local GPU path")
+        if page_slice is not None and not self.local:
+            raise ValueError("sliced reads use the local GPU path")
         self._check_segments(kv_out, page_offsets, page_elems, segments,
-                             segment_stride)
+                             segment_stride, page_slice)
         try:
             if self.local:
                 self.conn.read_pages(kv_out, keys, page_offsets, page_elems,
                                      segments=segments,
-                                     segment_stride=segment_stride)
+                                     segment_stride=segment_stride,
+                                     page_slice=page_slice)
             else:
                 self._ensure_mr(kv_out)
                 blocks = [(k, int(o)) for k, o in zip(keys, page_offsets)]
@@ -138,23 +142,27 @@ class PagedKVConnector:
 
     def load_layer_async(self, layer: int, kv_out: torch.Tensor,
                          page_keys: List[str], page_offsets, page_elems: int,
-                         segments: int = 1, segment_stride: int = 0):
+                         segments: int = 1, segment_stride: int = 0,
+                         page_slice=None):
         """Ticketed prefetch (local path): push the gather and return a
         ticket; call wait_load(ticket) before touching kv_out. Lets decode
         overlap the next request's KV fetch with current compute. Returns
         None if any page was missing or the path is unavailable (caller
-        falls back to load_layer / recompute)."""
+        falls back to load_layer / recompute). page_slice as in load_layer."""
         if not self.local:
             if segments != 1:
                 raise ValueError("segmented pages use the local GPU path")
+            if page_slice is not None:
+                raise ValueError("sliced reads use the local GPU path")
             return None
         keys = [self._key(layer, k) for k in page_keys]
         self._check_segments(kv_out, page_offsets, page_elems, segments,
-                             segment_stride)
+                             segment_stride, page_slice)
         try:
             return self.conn.read_pages_async(kv_out, keys, page_offsets,
                                               page_elems, segments=segments,
-                                              segment_stride=segment_stride)
+                                              segment_stride=segment_stride,
+                                              page_slice=page_slice)
         except Exception:
             return None
 
@@ -173,9 +181,12 @@ class PagedKVConnector:
 
     # -- internals ------------------------------------------------------------
     def _check_segments(self, kv: torch.Tensor, page_offsets, page_elems: int,
-                        segments: int, segment_stride: int):
+                        segments: int, segment_stride: int, page_slice=None):
         # The loads turn every failure into False / None; a refused geometry
         # is the caller's mistake and stays a ValueError.
+        if page_slice is not None:
+            self.conn._check_slice(kv.numel(), page_offsets, page_elems, page_slice,
+                                   segments, segment_stride)
         self.conn._check_segments(kv.numel(), kv.element_size(), page_offsets,
                                   page_elems, segments, segment_stride)
 

@@ -20,7 +20,7 @@ Differences (MI355X-native build):
 import os
 import time
 import asyncio
-from typing import List, Optional, Tuple
+from typing import List, NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
@@ -258,6 +258,22 @@ def _remap_device_id(tensor: torch.Tensor) -> int:
     return device_id
 
 
+class PageSlice(NamedTuple):
+    """Pool-side geometry of a sliced read, in ELEMENTS of the cache tensor:
+    from every stored page of `page_size` elements take `count` pieces of
+    `piece` elements, piece p starting at element offset + p * stride of the
+    page. The reader receives the concatenation, a page of count * piece
+    elements (docs/design.md, "sliced reads"). Read-only: there is no sliced
+    write. E.g. the heads h0..h1 of a [2, T, H, hd] page:
+    PageSlice(2*T*H*hd, h0*hd, (h1-h0)*hd, H*hd, 2*T)."""
+
+    page_size: int  # of the page as it was WRITTEN
+    offset: int  # of piece 0 inside that page
+    piece: int
+    stride: int = 0  # from one piece to the next (ignored for count == 1)
+    count: int = 1
+
+
 class InfinityConnection:
     """Connection to an infinistore-amd server (local IPC path or
     RDMA-semantics path over the negotiated fabric)."""
@@ -402,9 +418,52 @@ class InfinityConnection:
                              > numel):
             raise ValueError("a segmented page extends outside the tensor")
 
+    # Sliced reads (csrc/core/page_codec.h, docs/design.md): the most pieces
+    # one slice may have; tests/test_page_slice.py checks it against the
+    # native constant.
+    MAX_SLICE_PIECES = 4096
+
+    @classmethod
+    def _check_slice(cls, numel: int, offsets, page_size: int, page_slice,
+                     segments: int = 1, segment_stride: int = 0) -> None:
+        """Refuse (ValueError) a sliced read the store cannot serve, before
+        anything is sent: slice_legal's plain rules in elements (the server
+        checks each stored page's own codec), page_size == count * piece, and
+        the bound check that keeps every sliced page inside the tensor."""
+        sl = PageSlice(*page_slice)
+        if not 1 <= sl.count <= cls.MAX_SLICE_PIECES:
+            raise ValueError(f"PageSlice.count must be in 1..{cls.MAX_SLICE_PIECES}")
+        if sl.piece <= 0:
+            raise ValueError("PageSlice.piece must be positive")
+        if sl.offset < 0 or sl.page_size <= 0:
+            raise ValueError("PageSlice.offset and page_size must not be negative")
+        if sl.count > 1 and sl.stride < sl.piece:
+            raise ValueError("PageSlice.stride is smaller than a piece: the pieces "
+                             "would overlap")
+        span = (sl.count - 1) * sl.stride if sl.count > 1 else 0
+        if sl.offset + span + sl.piece > sl.page_size:
+            raise ValueError("the slice extends outside the stored page")
+        if page_size != sl.count * sl.piece:
+            raise ValueError("page_size must be PageSlice.count * PageSlice.piece, the "
+                             "size of the sliced page")
+        if segments > 1 and sl.count % segments != 0:
+            raise ValueError("PageSlice.count must be a multiple of segments: a piece "
+                             "never straddles a segment")
+        if segments == 1 and len(offsets) and int(max(offsets)) + page_size > numel:
+            raise ValueError("a sliced page extends outside the tensor")
+        # segments > 1: _check_segments bounds the segmented sliced page
+
+    @staticmethod
+    def _slice_arg(page_slice):
+        """The native (n_pieces, page, offset, piece, stride) tuple, or None."""
+        if page_slice is None:
+            return None
+        sl = PageSlice(*page_slice)
+        return (sl.count, sl.page_size, sl.offset, sl.piece, sl.stride)
+
     def write_pages(self, cache: torch.Tensor, keys, offsets, page_size: int,
                     sync: bool = False, quant: Optional[str] = None,
-                    segments: int = 1, segment_stride: int = 0):
+                    segments: int = 1, segment_stride: int = 0, **unsupported):
         """sync=True completes the write in ONE round trip (the response is
         sent when the copy finishes); sync=False (default) returns after the
         server accepts, so uploads overlap compute — call sync() later.
@@ -437,7 +496,15 @@ class InfinityConnection:
         of the pieces, byte-identical to a contiguous write of it, so any
         reader, contiguous or segmented with any S, can fetch it. Local path
         only; an illegal geometry or a page that leaves the tensor is a
-        ValueError before anything is sent."""
+        ValueError before anything is sent.
+
+        Slices are read-only: write_pages has no page_slice parameter, and
+        passing one is a ValueError."""
+        if "page_slice" in unsupported:
+            raise ValueError("page_slice is read-only: there is no sliced write")
+        if unsupported:
+            raise TypeError(f"write_pages() got an unexpected keyword argument "
+                            f"{next(iter(unsupported))!r}")
         self._verify(cache)
         if segments != 1 and not self.local_connected:
             raise ValueError("segmented pages use the local GPU path")
@@ -478,29 +545,46 @@ class InfinityConnection:
         return 0
 
     def read_pages(self, cache: torch.Tensor, keys, offsets, page_size: int,
-                   segments: int = 1, segment_stride: int = 0):
+                   segments: int = 1, segment_stride: int = 0,
+                   page_slice: Optional[PageSlice] = None):
         """segments / segment_stride: scatter each page into that many equal
         pieces of `cache` (see write_pages), however the page was written.
-        Local path only."""
+        Local path only.
+
+        page_slice: fetch only that strided part of every stored page (see
+        PageSlice), e.g. a decode rank's heads of pages a prefill engine
+        stored under another tensor-parallel degree. page_size is then the
+        SLICED page, count * piece, and segments apply to it (count must be a
+        multiple of segments). Every key must have been written with
+        page_slice.page_size elements; for fp8 and mxfp4 pages offset, piece
+        and stride are multiples of 8 and 32 elements (the server answers
+        INVALID_REQ otherwise). Only the requested elements are read and
+        dequantized. Local path only; an illegal geometry or a page that
+        leaves the tensor is a ValueError before anything is sent."""
         self._verify(cache)
         if segments != 1 and not self.local_connected:
             raise ValueError("segmented pages use the local GPU path")
+        if page_slice is not None and not self.local_connected:
+            raise ValueError("sliced reads use the local GPU path")
         es = cache.element_size()
         if self.local_connected:
             offs = np.asarray(offsets, dtype=np.uint64)
+            if page_slice is not None:
+                self._check_slice(cache.numel(), offs, page_size, page_slice, segments,
+                                  segment_stride)
             self._check_segments(cache.numel(), es, offs, page_size, segments,
                                  segment_stride)
             if isinstance(keys, (bytes, bytearray, memoryview)):
                 ret = self.conn.rw_local_blob(
                     self.OP_R, keys, offs, es, page_size * es,
                     cache.data_ptr(), _remap_device_id(cache), False, 0,
-                    segments, segment_stride,
+                    segments, segment_stride, self._slice_arg(page_slice),
                 )
             else:
                 ret = self.conn.rw_local_keys(
                     self.OP_R, keys, offs, es, page_size * es,
                     cache.data_ptr(), _remap_device_id(cache), False, 0,
-                    segments, segment_stride,
+                    segments, segment_stride, self._slice_arg(page_slice),
                 )
         elif self.rdma_connected:
             blocks = [(k, int(o) * es) for k, o in zip(keys, offsets)]
@@ -511,19 +595,25 @@ class InfinityConnection:
             raise Exception(f"Failed to read from infinistore, ret = {ret}")
 
     def read_pages_async(self, cache: torch.Tensor, keys, offsets, page_size: int,
-                         segments: int = 1, segment_stride: int = 0):
+                         segments: int = 1, segment_stride: int = 0,
+                         page_slice: Optional[PageSlice] = None):
         """Ticketed read (local path, shm ring): pushes the request and
         returns a ticket; call wait_read(ticket) before using the data. Lets
         an engine overlap its own work (or further requests) with the copy —
         e.g. prefetching the next sequence's KV pages while decoding. Falls
         back to a blocking read (ticket 0) when the ring is unavailable.
-        segments / segment_stride as in read_pages."""
+        segments / segment_stride / page_slice as in read_pages."""
         self._verify(cache)
         if segments != 1 and not self.local_connected:
             raise ValueError("segmented pages use the local GPU path")
+        if page_slice is not None and not self.local_connected:
+            raise ValueError("sliced reads use the local GPU path")
         assert self.local_connected, "read_pages_async uses the local GPU path"
         es = cache.element_size()
         offs = np.asarray(offsets, dtype=np.uint64)
+        if page_slice is not None:
+            self._check_slice(cache.numel(), offs, page_size, page_slice, segments,
+                              segment_stride)
         self._check_segments(cache.numel(), es, offs, page_size, segments,
                              segment_stride)
         if not isinstance(keys, (bytes, bytearray, memoryview)):
@@ -531,6 +621,7 @@ class InfinityConnection:
         ret, ticket = self.conn.rw_local_blob_async(
             self.OP_R, keys, offs, es, page_size * es,
             cache.data_ptr(), _remap_device_id(cache), segments, segment_stride,
+            self._slice_arg(page_slice),
         )
         if ret < 0:
             raise Exception(f"Failed to read from infinistore, ret = {ret}")

@@ -44,6 +44,7 @@ from typing import Dict, List, Optional, Sequence
 import torch
 
 from .kv_connector import PagedKVConnector, token_page_hashes
+from .lib import PageSlice
 
 
 class InfiniStoreKVAdapter:
@@ -71,13 +72,44 @@ class InfiniStoreKVAdapter:
         kv_layout: "block_major" or "kv_major" (see the module docstring).
             page_elems counts K plus V in both. "kv_major" needs the local
             path (ValueError with local=False).
+        stored_kv_heads, head_range, head_dim: mixed tensor-parallel decode.
+            The pages in the store are a prefill engine's
+            ``[2, block_tokens, stored_kv_heads, head_dim]``; this engine owns
+            the KV heads ``head_range = (h0, h1)`` of them, so its own
+            page_elems is ``2*block_tokens*(h1-h0)*head_dim`` (checked) and
+            every load is a sliced read (docs/design.md, "sliced reads") that
+            fetches only those heads. Works in both layouts and needs the
+            local path. Such an adapter is load-only: save_kv_layer raises
+            ValueError. Keys and prefix lookups are the prefill engine's.
     """
 
     KV_LAYOUTS = ("block_major", "kv_major")
 
     def __init__(self, host: str, port: int, model_tag: str, n_layers: int,
                  block_tokens: int, page_elems: int, local: bool = True,
-                 quant: Optional[str] = None, kv_layout: str = "block_major"):
+                 quant: Optional[str] = None, kv_layout: str = "block_major",
+                 stored_kv_heads: Optional[int] = None,
+                 head_range: Optional[Sequence[int]] = None,
+                 head_dim: Optional[int] = None):
+        self._page_slice = None
+        if head_range is not None:
+            if stored_kv_heads is None or head_dim is None:
+                raise ValueError("head_range needs stored_kv_heads and head_dim")
+            if not local:
+                raise ValueError("head_range uses sliced reads, which need the "
+                                 "local GPU path")
+            h0, h1 = (int(h) for h in head_range)
+            if not 0 <= h0 < h1 <= stored_kv_heads or head_dim <= 0:
+                raise ValueError("head_range must be 0 <= h0 < h1 <= stored_kv_heads")
+            if page_elems != 2 * block_tokens * (h1 - h0) * head_dim:
+                raise ValueError("with head_range=(h0, h1) page_elems is "
+                                 "2*block_tokens*(h1-h0)*head_dim")
+            self._page_slice = PageSlice(
+                page_size=2 * block_tokens * stored_kv_heads * head_dim,
+                offset=h0 * head_dim, piece=(h1 - h0) * head_dim,
+                stride=stored_kv_heads * head_dim, count=2 * block_tokens)
+        elif stored_kv_heads is not None or head_dim is not None:
+            raise ValueError("stored_kv_heads and head_dim go with head_range")
         if kv_layout not in self.KV_LAYOUTS:
             raise ValueError(f"kv_layout must be one of {self.KV_LAYOUTS}")
         if kv_layout == "kv_major":
@@ -123,6 +155,9 @@ class InfiniStoreKVAdapter:
         ``block_table[p]`` names the physical block of logical page ``p``.
         ``skip_leading_pages`` skips pages already known cached (prefix
         hits reported by the scheduler)."""
+        if self._page_slice is not None:
+            raise ValueError("an adapter with head_range is load-only: slices "
+                             "are a read-side geometry")
         keys = self._page_keys(token_ids)
         n_pages = len(keys)
         if n_pages > len(block_table):
@@ -198,10 +233,14 @@ class InfiniStoreKVAdapter:
 
     def _geometry(self, kv_cache: torch.Tensor) -> dict:
         """Segment arguments for one layer tensor: none for block_major; K
-        and V halves a plane (half the tensor) apart for kv_major."""
-        if self.kv_layout != "kv_major":
-            return {}
-        return {"segments": 2, "segment_stride": kv_cache.numel() // 2}
+        and V halves a plane (half the tensor) apart for kv_major. With a
+        head_range, the slice every load takes (saves never get here)."""
+        geo = {}
+        if self._page_slice is not None:
+            geo["page_slice"] = self._page_slice
+        if self.kv_layout == "kv_major":
+            geo.update(segments=2, segment_stride=kv_cache.numel() // 2)
+        return geo
 
     def _page_keys(self, token_ids: Sequence[int]) -> List[str]:
         ck = tuple(token_ids)
