@@ -400,10 +400,12 @@ int ClientConn::rw_local_packed(char op, const char* keys_blob, size_t blob_len,
                                 uintptr_t ptr, int device_id, bool sync_response,
                                 uint64_t* out_ticket, uint32_t extra_flags,
                                 uint32_t n_segments, uint64_t segment_stride,
-                                const PackedLocalSliceExt* slice) {
+                                const PackedLocalSliceExt* slice,
+                                const PackedLocalTensorExt* tset) {
     if (out_ticket) *out_ticket = 0;  // 0 = completed synchronously
     if (!connected_) return -1;
     if (slice && slice->n_pieces != 0 && op != 'R') return -INVALID_REQ;  // read-only
+    if (slice && slice->n_pieces != 0 && tset) return -INVALID_REQ;  // not together
     if (!gpu::available()) {
         ERROR("local path requires a GPU");
         return -1;
@@ -411,7 +413,12 @@ int ClientConn::rw_local_packed(char op, const char* keys_blob, size_t blob_len,
     gpu::IpcHandle handle;
     uint64_t base_offset = 0;
     uint64_t alloc_size = 0;
-    {
+    if (tset) {
+        // The set's tensors were exported at registration: the header's
+        // handle, base and allocation size are ignored, and sent as zeros.
+        memset(handle.bytes, 0, gpu::kIpcHandleSize);
+        ptr = 0;
+    } else {
         std::lock_guard<std::mutex> lk(ipc_mu_);
         auto it = ipc_export_cache_.find(ptr);
         if (it != ipc_export_cache_.end()) {
@@ -451,7 +458,7 @@ int ClientConn::rw_local_packed(char op, const char* keys_blob, size_t blob_len,
     memcpy(h.ipc, handle.bytes, gpu::kIpcHandleSize);
 
     std::vector<uint8_t> body =
-        build_packed_local(h, n_segments, segment_stride, offsets, keys_blob, blob_len, slice);
+        build_packed_local(h, n_segments, segment_stride, offsets, keys_blob, blob_len, slice, tset);
 
     char wire_op = (op == 'W') ? OP_W_FAST : OP_R_FAST;
     static const bool dbg = getenv("IFS_CLIENT_DEBUG") != nullptr;
@@ -494,6 +501,51 @@ int ClientConn::rw_local_packed(char op, const char* keys_blob, size_t blob_len,
     }
     if (op == 'W' && !sync_response) local_dirty_ = true;  // sync RTT needed
     return 0;
+}
+
+int ClientConn::register_tensor_set(const std::vector<uintptr_t>& ptrs,
+                                    const std::vector<uint64_t>& extents, int device_id) {
+    if (!connected_) return -1;
+    if (ptrs.empty() || ptrs.size() > kMaxPageTensors || ptrs.size() != extents.size())
+        return -INVALID_REQ;
+    if (!gpu::available()) {
+        ERROR("local path requires a GPU");
+        return -1;
+    }
+    std::vector<PackedTensorRec> recs(ptrs.size());
+    for (size_t g = 0; g < ptrs.size(); g++) {
+        gpu::IpcHandle handle;
+        uint64_t base_offset = 0, alloc_size = 0;
+        if (!gpu::ipc_export(reinterpret_cast<void*>(ptrs[g]), &handle, &base_offset,
+                             &alloc_size))
+            memset(handle.bytes, 0, gpu::kIpcHandleSize);  // same-process servers need none
+        PackedTensorRec& r = recs[g];
+        r.base_ptr = ptrs[g] - base_offset;
+        r.base_offset = base_offset;
+        r.extent_bytes = extents[g];
+        r.alloc_mb = static_cast<uint32_t>((alloc_size + (1 << 20) - 1) >> 20);
+        r.rsvd = 0;
+        memcpy(r.ipc, handle.bytes, gpu::kIpcHandleSize);
+    }
+    std::vector<uint8_t> body =
+        build_tensor_set(static_cast<int32_t>(getpid()), device_id, recs);
+    std::lock_guard<std::mutex> lk(io_mu_);
+    if (!send_req(OP_TSET_REGISTER, body.data(), body.size())) return -1;
+    int code = 0;
+    if (!recv_status(&code)) return -1;
+    if (code != FINISH) return code > 0 ? -code : -1;
+    uint32_t id = 0;
+    if (!recv_exact(fd_, &id, 4)) return -1;
+    return static_cast<int>(id);
+}
+
+int ClientConn::release_tensor_set(uint32_t set_id) {
+    if (!connected_) return -1;
+    std::lock_guard<std::mutex> lk(io_mu_);
+    if (!send_req(OP_TSET_RELEASE, reinterpret_cast<const uint8_t*>(&set_id), sizeof(set_id))) return -1;
+    int code = 0;
+    if (!recv_status(&code)) return -1;
+    return code == FINISH ? 0 : (code > 0 ? -code : -1);
 }
 
 int ClientConn::sync_local() {

@@ -75,7 +75,18 @@ class ClientConn {
                         int device_id, bool sync_response = false,
                         uint64_t* out_ticket = nullptr, uint32_t extra_flags = 0,
                         uint32_t n_segments = 1, uint64_t segment_stride = 0,
-                        const PackedLocalSliceExt* slice = nullptr);
+                        const PackedLocalSliceExt* slice = nullptr,
+                        const PackedLocalTensorExt* tset = nullptr);
+    // Tensor sets (docs/design.md, "tensor sets"): register the tensors at
+    // ptrs[g] (extents[g] bytes each, all on device_id) as one ordered set on
+    // this connection; returns the set id (> 0) or a negative status. A
+    // request that passes `tset` to rw_local_packed addresses the set: ptr is
+    // ignored, offsets are relative to each tensor, n_segments is the total
+    // over all tensors. With a slice as well it returns -INVALID_REQ without
+    // sending anything.
+    int register_tensor_set(const std::vector<uintptr_t>& ptrs,
+                            const std::vector<uint64_t>& extents, int device_id);
+    int release_tensor_set(uint32_t set_id);
     // Wait for a ticketed (async shm) op; ticket 0 = already complete.
     int wait_local_ticket(uint64_t ticket);
     int sync_local();

@@ -118,6 +118,30 @@ inline bool segments_legal(PageCodec c, size_t page_bytes, uint64_t n_segments,
     return true;
 }
 
+// Tensor sets (docs/design.md, "tensor sets"): on the CLIENT side of one
+// request a page may span n_tensors tensors, an equal part of the page in each
+// and every part at the SAME byte offset inside its own tensor. A part may
+// itself be segmented: with n_segments segments in the whole page, segment s
+// lives at base[s / (S/G)] + offset + (s % (S/G)) * stride_bytes. The stored
+// block is still that of the concatenation. The bound is a condition, not a
+// tuning value: the table of bases is 1 KiB, and the largest current open
+// models have 126 layers. kMaxPageSegments still bounds the total S.
+constexpr uint32_t kMaxPageTensors = 128;
+
+// The one predicate for a page over a tensor set, used by every layer as
+// segments_legal is. n_segments is the TOTAL over all tensors. With one
+// segment per tensor (S/G == 1) no stride is ever applied, so it is ignored;
+// the whole page otherwise obeys segments_legal.
+inline bool tensors_legal(PageCodec c, size_t page_bytes, uint64_t n_segments,
+                          uint64_t stride_bytes, uint64_t n_tensors) {
+    if (n_tensors < 1 || n_tensors > kMaxPageTensors) return false;
+    if (n_segments < 1 || n_segments % n_tensors != 0) return false;
+    // A stride that is never applied stands in as the segment's own size,
+    // which segments_legal accepts exactly when the segment itself is legal.
+    if (n_segments == n_tensors) stride_bytes = page_bytes / n_segments;
+    return segments_legal(c, page_bytes, n_segments, stride_bytes);
+}
+
 // Sliced reads (docs/design.md, "sliced reads"): on the POOL side of a read a
 // request may take n equal pieces of the stored page, piece p starting at
 // logical byte offset + p * stride; the client receives their concatenation,

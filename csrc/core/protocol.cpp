@@ -161,14 +161,17 @@ bool parse_match_request(const uint8_t* buf, size_t len, std::vector<std::string
 std::vector<uint8_t> build_packed_local(PackedLocalHdr h, uint32_t n_segments,
                                         uint64_t segment_stride, const uint64_t* offsets,
                                         const char* keys_blob, size_t blob_len,
-                                        const PackedLocalSliceExt* slice) {
+                                        const PackedLocalSliceExt* slice,
+                                        const PackedLocalTensorExt* tset) {
     const size_t n = h.n_blocks;
     const bool seg = n_segments != 1;
     const bool sliced = slice && slice->n_pieces != 0;
     if (seg) h.flags |= kLocalFlagSegmented;
     if (sliced) h.flags |= kLocalFlagSliced;
+    if (tset) h.flags |= kLocalFlagTensorSet;
     const size_t seg_ext = seg ? sizeof(PackedLocalSegExt) : 0;
-    const size_t ext = seg_ext + (sliced ? sizeof(PackedLocalSliceExt) : 0);
+    const size_t slice_end = seg_ext + (sliced ? sizeof(PackedLocalSliceExt) : 0);
+    const size_t ext = slice_end + (tset ? sizeof(PackedLocalTensorExt) : 0);
     std::vector<uint8_t> body(sizeof(h) + ext + n * 8 + blob_len);
     memcpy(body.data(), &h, sizeof(h));
     if (seg) {
@@ -176,6 +179,7 @@ std::vector<uint8_t> build_packed_local(PackedLocalHdr h, uint32_t n_segments,
         memcpy(body.data() + sizeof(h), &e, sizeof(e));
     }
     if (sliced) memcpy(body.data() + sizeof(h) + seg_ext, slice, sizeof(*slice));
+    if (tset) memcpy(body.data() + sizeof(h) + slice_end, tset, sizeof(*tset));
     if (n) memcpy(body.data() + sizeof(h) + ext, offsets, n * 8);
     if (blob_len) memcpy(body.data() + sizeof(h) + ext + n * 8, keys_blob, blob_len);
     return body;
@@ -188,6 +192,10 @@ bool parse_packed_local(char op, const uint8_t* body, size_t body_len, PackedLoc
     size_t pos = sizeof(h);
     out->n_segments = 1;
     out->segment_stride = 0;
+    // Over a tensor set the geometry is judged once the set's extension has
+    // been read, by tensors_legal.
+    const bool has_tset = (h.flags & kLocalFlagTensorSet) != 0;
+    if (has_tset && (h.flags & kLocalFlagSliced)) return false;
     if (h.flags & kLocalFlagSegmented) {
         if (body_len < pos + sizeof(PackedLocalSegExt)) return false;
         PackedLocalSegExt e;
@@ -196,7 +204,8 @@ bool parse_packed_local(char op, const uint8_t* body, size_t body_len, PackedLoc
         if (e.rsvd != 0) return false;
         PageCodec codec = PageCodec::kNone;
         if (op == OP_W_FAST && !page_codec_from_flags(h.flags, &codec)) return false;
-        if (!segments_legal(codec, h.block_size, e.n_segments, e.segment_stride)) return false;
+        if (!has_tset && !segments_legal(codec, h.block_size, e.n_segments, e.segment_stride))
+            return false;
         out->n_segments = e.n_segments;
         out->segment_stride = e.segment_stride;
     }
@@ -216,6 +225,21 @@ bool parse_packed_local(char op, const uint8_t* body, size_t body_len, PackedLoc
         if (h.block_size != e.n_pieces * e.piece_bytes) return false;
         out->slice = e;
     }
+    out->has_tset = has_tset;
+    out->tset = PackedLocalTensorExt{};
+    if (has_tset) {
+        if (body_len < pos + sizeof(PackedLocalTensorExt)) return false;
+        PackedLocalTensorExt e;
+        memcpy(&e, body + pos, sizeof(e));
+        pos += sizeof(e);
+        if (e.rsvd != 0) return false;
+        PageCodec codec = PageCodec::kNone;
+        if (op == OP_W_FAST && !page_codec_from_flags(h.flags, &codec)) return false;
+        if (!tensors_legal(codec, h.block_size, out->n_segments, out->segment_stride,
+                           e.n_tensors))
+            return false;
+        out->tset = e;
+    }
     const size_t n = h.n_blocks;
     const size_t off_end = pos + n * 8;
     if (body_len < off_end) return false;
@@ -233,6 +257,29 @@ bool parse_packed_local(char op, const uint8_t* body, size_t body_len, PackedLoc
         out->blocks.push_back({std::string_view(kp, ke - kp), off});
         kp = nul ? nul + 1 : kend;
     }
+    return true;
+}
+
+std::vector<uint8_t> build_tensor_set(int32_t pid, int32_t device,
+                                      const std::vector<PackedTensorRec>& recs) {
+    PackedTensorSetHdr h{pid, device, static_cast<uint32_t>(recs.size()), 0};
+    std::vector<uint8_t> body(sizeof(h) + recs.size() * sizeof(PackedTensorRec));
+    memcpy(body.data(), &h, sizeof(h));
+    if (!recs.empty())
+        memcpy(body.data() + sizeof(h), recs.data(), recs.size() * sizeof(PackedTensorRec));
+    return body;
+}
+
+bool parse_tensor_set(const uint8_t* body, size_t body_len, PackedTensorSetHdr* hdr,
+                      std::vector<PackedTensorRec>* recs) {
+    if (body_len < sizeof(*hdr)) return false;
+    memcpy(hdr, body, sizeof(*hdr));
+    if (hdr->rsvd != 0 || hdr->n_tensors < 1 || hdr->n_tensors > kMaxPageTensors) return false;
+    if (body_len != sizeof(*hdr) + hdr->n_tensors * sizeof(PackedTensorRec)) return false;
+    recs->resize(hdr->n_tensors);
+    memcpy(recs->data(), body + sizeof(*hdr), hdr->n_tensors * sizeof(PackedTensorRec));
+    for (const PackedTensorRec& r : *recs)
+        if (r.rsvd != 0) return false;
     return true;
 }
 

@@ -56,8 +56,9 @@ constexpr char OP_STATS = 'Q';    // server stats JSON over the wire (extension)
 // flat binary layout the hot path can build/parse at memcpy speed — the
 // flatbuffers LocalMetaRequest ops remain accepted for wire compatibility.
 // Body: PackedLocalHdr, [PackedLocalSegExt when kLocalFlagSegmented is set,]
-// [PackedLocalSliceExt when kLocalFlagSliced is set,] u64 offsets[n],
-// NUL-separated key bytes (n keys).
+// [PackedLocalSliceExt when kLocalFlagSliced is set,] [PackedLocalTensorExt
+// when kLocalFlagTensorSet is set,] u64 offsets[n], NUL-separated key bytes
+// (n keys).
 constexpr char OP_W_FAST = 'w';
 constexpr char OP_R_FAST = 'r';
 // Shared-memory ring handshake (extension, same-host clients): body is the
@@ -65,6 +66,15 @@ constexpr char OP_R_FAST = 'r';
 // FINISH response the client sends OP_W_FAST/OP_R_FAST/OP_SYNC through the
 // ring instead of the socket.
 constexpr char OP_SHM_SETUP = 'h';
+// Tensor sets (extension; docs/design.md, "tensor sets"): register an ordered
+// list of client tensors on this connection once, then name it in packed
+// requests by id. Socket only. Register body: PackedTensorSetHdr + n_tensors
+// PackedTensorRec; the reply is FINISH + u32 set id, or a bare error status.
+// Release body: u32 set id; the reply is a bare status.
+constexpr char OP_TSET_REGISTER = 't';
+constexpr char OP_TSET_RELEASE = 'u';
+// Live sets one connection may hold.
+constexpr uint32_t kMaxTensorSetsPerConn = 16;
 
 #pragma pack(push, 1)
 struct PackedLocalHdr {
@@ -109,6 +119,40 @@ struct PackedLocalSliceExt {
 #pragma pack(pop)
 static_assert(sizeof(PackedLocalSliceExt) == 40, "packed local slice extension size");
 
+// Follows PackedLocalHdr and the segment and slice extensions when
+// kLocalFlagTensorSet is set, so that the existing prefixes parse as before:
+// the request's pages span the tensors of a registered set. The header's ipc,
+// base_ptr and base_offset are then ignored, and offsets[] are relative to
+// each tensor.
+#pragma pack(push, 1)
+struct PackedLocalTensorExt {
+    uint32_t set_id;
+    uint32_t n_tensors;  // must equal the registered count
+    uint64_t rsvd;       // 0
+};
+#pragma pack(pop)
+static_assert(sizeof(PackedLocalTensorExt) == 16, "packed local tensor-set extension size");
+
+// OP_TSET_REGISTER body: this header, then n_tensors records in set order.
+#pragma pack(push, 1)
+struct PackedTensorSetHdr {
+    int32_t pid;
+    int32_t device;
+    uint32_t n_tensors;
+    uint32_t rsvd;  // 0
+};
+struct PackedTensorRec {
+    uint64_t base_ptr;      // the allocation's base in the client's address space
+    uint64_t base_offset;   // the tensor's first byte inside the allocation
+    uint64_t extent_bytes;  // the tensor's size: no page part may reach past it
+    uint32_t alloc_mb;      // allocation size in MB (0 = unknown), as PackedLocalHdr.rsvd
+    uint32_t rsvd;          // 0
+    uint8_t ipc[64];
+};
+#pragma pack(pop)
+static_assert(sizeof(PackedTensorSetHdr) == 16 && sizeof(PackedTensorRec) == 96,
+              "tensor set registration sizes");
+
 // PackedLocalHdr.flags: defer the response until the copy completes (one
 // round trip instead of request-ack + sync).
 constexpr uint32_t kLocalFlagSyncResponse = 1;
@@ -128,6 +172,10 @@ constexpr uint32_t kLocalFlagSegmented = 8;
 // given by the PackedLocalSliceExt that follows the header and the segment
 // extension (extension; OP_R_FAST only, INVALID_REQ on OP_W_FAST).
 constexpr uint32_t kLocalFlagSliced = 16;
+// The pages span the tensors of a registered set, named by the
+// PackedLocalTensorExt that follows the other extensions (extension; both
+// packed ops). Together with kLocalFlagSliced it is INVALID_REQ.
+constexpr uint32_t kLocalFlagTensorSet = 32;
 
 std::string op_name(char op);
 
@@ -203,7 +251,18 @@ bool parse_match_request(const uint8_t* buf, size_t len, std::vector<std::string
 std::vector<uint8_t> build_packed_local(PackedLocalHdr h, uint32_t n_segments,
                                         uint64_t segment_stride, const uint64_t* offsets,
                                         const char* keys_blob, size_t blob_len,
-                                        const PackedLocalSliceExt* slice = nullptr);
+                                        const PackedLocalSliceExt* slice = nullptr,
+                                        const PackedLocalTensorExt* tset = nullptr);
+// (The tensor-set extension and kLocalFlagTensorSet are written only when
+// `tset` is given; the segment extension is then written for n_segments > 1
+// as always, n_segments being the total over all tensors.)
+
+// OP_TSET_REGISTER body and its parser (false: truncated, rsvd set, or a
+// count outside 1..kMaxPageTensors).
+std::vector<uint8_t> build_tensor_set(int32_t pid, int32_t device,
+                                      const std::vector<PackedTensorRec>& recs);
+bool parse_tensor_set(const uint8_t* body, size_t body_len, PackedTensorSetHdr* hdr,
+                      std::vector<PackedTensorRec>* recs);
 
 // Parsed view of a packed body: (key, byte offset) per block, the key views
 // pointing into the body. The server moves `blocks` into its request view,
@@ -213,6 +272,8 @@ struct PackedLocalReq {
     uint32_t n_segments = 1;
     uint64_t segment_stride = 0;
     PackedLocalSliceExt slice{};  // n_pieces == 0: whole pages
+    bool has_tset = false;
+    PackedLocalTensorExt tset{};
     std::vector<std::pair<std::string_view, uint64_t>> blocks;
 };
 // False (the server answers INVALID_REQ) for a truncated body or extension,
@@ -221,7 +282,10 @@ struct PackedLocalReq {
 // pages on OP_R_FAST (the read path re-checks every entry against its own
 // codec once the index has told it what the keys hold). kLocalFlagSliced is
 // refused on OP_W_FAST; on OP_R_FAST also when block_size is not n_pieces *
-// piece_bytes or slice_legal refuses the geometry under plain rules.
+// piece_bytes or slice_legal refuses the geometry under plain rules. With
+// kLocalFlagTensorSet the geometry rule is tensors_legal instead of
+// segments_legal (same codec choice), and the flag together with
+// kLocalFlagSliced is refused.
 bool parse_packed_local(char op, const uint8_t* body, size_t body_len, PackedLocalReq* out);
 
 // Sentinel for duplicate-key allocations: the server returns rkey=0, addr=0

@@ -135,6 +135,37 @@ bool launch_transform_blocks(int dev, Stream s, PageCodec codec, PageDir dir,
 // loop iteration (four lanes per group).
 constexpr int kMxfp4GroupsPerIter = 64;
 
+// --- tensor sets --------------------------------------------------------------
+// The client side of every page spans tset.n tensors (core/page_codec.h,
+// tensors_legal; docs/design.md, "tensor sets"): seg.n is the TOTAL segment
+// count S, and segment s of block i lives at
+//   tset.bases[s / (S/G)] + client_desc[i] + (s % (S/G)) * seg.stride_bytes.
+// The client descriptor (src for kStore, dst for kLoad) is therefore a byte
+// OFFSET, the same inside every tensor; the pool descriptor is a pointer, and
+// both arrays are device-visible as above. tset.bases is HOST memory: the
+// table is copied into the kernel arguments at launch, so it need not outlive
+// the call.
+struct TensorTable {
+    const uint64_t* bases = nullptr;  // n device addresses, host array
+    uint32_t n = 0;
+};
+// Plain pages: the 16 B/lane kernel when aligned16 holds (every offset and
+// pool pointer is a multiple of 16; the CALLER checks, the descriptors may be
+// device memory) and every base, the segment size and, where one is applied,
+// the stride are multiples of 16 too; else the byte kernel. False before any
+// launch for a geometry tensors_legal refuses or a grid that does not fit.
+bool launch_copy_blocks_tset(int dev, Stream s, const uint64_t* dev_src, const uint64_t* dev_dst,
+                             int n_blocks, size_t bytes_per_block, bool aligned16,
+                             PageSegments seg, PageDir dir, TensorTable tset);
+// Transforming codecs, scales as for launch_transform_blocks: fp8 keeps ONE
+// scale per page over all tensors, mxfp4 indexes codes and scale bytes by the
+// page-global unit. There is no byte fallback: additionally false, before any
+// launch, unless aligned16 holds and every base is a multiple of 16.
+bool launch_transform_blocks_tset(int dev, Stream s, PageCodec codec, PageDir dir,
+                                  const uint64_t* dev_src, const uint64_t* dev_dst,
+                                  float* dev_scales, int n_blocks, size_t elems_per_block,
+                                  bool aligned16, PageSegments seg, TensorTable tset);
+
 // --- sliced reads -------------------------------------------------------------
 // Load direction only (core/page_codec.h, PageSlice; docs/design.md, "sliced
 // reads"): from each stored block take slice.n pieces of slice.piece_bytes

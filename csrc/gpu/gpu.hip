@@ -878,6 +878,344 @@ bool launch_transform_blocks(int dev, Stream stream, PageCodec codec, PageDir di
     return true;
 }
 
+// --- tensor sets ---------------------------------------------------------------
+// The client side of a page spans n_tensors tensors (gpu.h, docs/design.md
+// "tensor sets"): segment s of the page's S lies in tensor g = s / (S/G), at
+// base[g] + offset + (s % (S/G)) * stride, the offset being the block's client
+// descriptor. The mapping stays (block, segment, chunk) and the descriptor
+// pair is read once through LDS by block_seg_chunk_descs; g is a function of
+// blockIdx.x and kernel arguments alone, so base[g] is one scalar load per
+// workgroup and the unit loops are the segmented kernels' loops.
+//
+// The table of bases rides in the KERNEL ARGUMENTS, not in the slot's pinned
+// descriptor area. It is per request, not per block: 1 KiB that the launch
+// copies into the kernarg segment, which the device reads through the scalar
+// cache with a workgroup-uniform index, so no lane ever indexes it and nothing
+// spills to scratch. In the pinned area every workgroup would fetch its base
+// over PCIe (one more dependent host read before the first payload load, on
+// top of the descriptor pair), the slot layout would change for every job, and
+// fan-out sub-jobs on other streams would each stage their own copy. A kernel
+// argument also ends the table's lifetime question: it is copied at launch.
+struct TensorBases {
+    uint64_t base[kMaxPageTensors];
+};
+
+__global__ void copy_blocks_vec_tset_kernel(const uint64_t* __restrict__ src_ptrs,
+                                            const uint64_t* __restrict__ dst_ptrs,
+                                            uint32_t n_segments, uint32_t segs_per_tensor,
+                                            uint32_t chunks_per_seg, uint32_t to_pool,
+                                            uint64_t units_per_seg, uint64_t stride,
+                                            TensorBases tb) {
+    uint64_t sd[2];
+    uint32_t seg;
+    uint32_t chunk =
+        block_seg_chunk_descs(src_ptrs, dst_ptrs, n_segments, chunks_per_seg, sd, &seg);
+    uint32_t g = seg / segs_per_tensor;
+    uint32_t r = seg - g * segs_per_tensor;
+    uint64_t client = tb.base[g] + r * stride;
+    uint64_t pool = seg * (units_per_seg * 16);
+    const uint4* s = reinterpret_cast<const uint4*>(sd[0] + (to_pool ? client : pool));
+    uint4* d = reinterpret_cast<uint4*>(sd[1] + (to_pool ? pool : client));
+    uint64_t step = static_cast<uint64_t>(chunks_per_seg) * blockDim.x;
+    for (uint64_t u = static_cast<uint64_t>(chunk) * blockDim.x + threadIdx.x;
+         u < units_per_seg; u += step)
+        d[u] = s[u];
+}
+
+__global__ void copy_blocks_byte_tset_kernel(const uint64_t* __restrict__ src_ptrs,
+                                             const uint64_t* __restrict__ dst_ptrs,
+                                             uint32_t n_segments, uint32_t segs_per_tensor,
+                                             uint32_t chunks_per_seg, uint32_t to_pool,
+                                             uint64_t bytes_per_seg, uint64_t stride,
+                                             TensorBases tb) {
+    uint64_t sd[2];
+    uint32_t seg;
+    uint32_t chunk =
+        block_seg_chunk_descs(src_ptrs, dst_ptrs, n_segments, chunks_per_seg, sd, &seg);
+    uint32_t g = seg / segs_per_tensor;
+    uint32_t r = seg - g * segs_per_tensor;
+    uint64_t client = tb.base[g] + r * stride;
+    uint64_t pool = seg * bytes_per_seg;
+    const uint8_t* s = reinterpret_cast<const uint8_t*>(sd[0] + (to_pool ? client : pool));
+    uint8_t* d = reinterpret_cast<uint8_t*>(sd[1] + (to_pool ? pool : client));
+    uint64_t step = static_cast<uint64_t>(chunks_per_seg) * blockDim.x;
+    for (uint64_t u = static_cast<uint64_t>(chunk) * blockDim.x + threadIdx.x;
+         u < bytes_per_seg; u += step)
+        d[u] = s[u];
+}
+
+// fp8: one 512-thread workgroup per page over ALL tensors, because the scale
+// is the page's: pass 1 takes the absmax over every tensor's part before pass
+// 2 converts any. Tensor loop outside (one scalar load of base[g] each), then
+// the segmented kernel's segment and unit loops.
+__global__ void quant_blocks_bf16_fp8_tset_kernel(const uint64_t* __restrict__ src_offs,
+                                                  const uint64_t* __restrict__ dst_ptrs,
+                                                  float* __restrict__ scales,
+                                                  uint32_t n_tensors, uint32_t segs_per_tensor,
+                                                  uint64_t seg_elems, uint64_t src_stride,
+                                                  TensorBases tb) {
+    const uint64_t off = src_offs[blockIdx.x];
+    uint2* dst = reinterpret_cast<uint2*>(dst_ptrs[blockIdx.x]);
+    __shared__ uint32_t red[8];  // 512 threads / 64-wide wavefronts
+    __shared__ float scale_sh;
+    uint32_t m = 0;  // largest finite bf16 magnitude, as bits
+    uint64_t n8 = seg_elems / 8;
+    for (uint32_t g = 0; g < n_tensors; g++) {
+        const uint64_t src = tb.base[g] + off;
+        for (uint32_t sg = 0; sg < segs_per_tensor; sg++) {
+            const uint4* src4 = reinterpret_cast<const uint4*>(src + sg * src_stride);
+            for (uint64_t u = threadIdx.x; u < n8; u += blockDim.x) {
+                uint4 pk = src4[u];
+                const uint16_t* h = reinterpret_cast<const uint16_t*>(&pk);
+#pragma unroll
+                for (int i = 0; i < 8; i++) m = fp8::absmax_step(m, h[i]);
+            }
+        }
+    }
+    for (int o = 32; o; o >>= 1) m = max(m, __shfl_down(m, o, 64));
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t mm = red[0];
+        for (int w = 1; w < static_cast<int>(blockDim.x) / 64; w++) mm = max(mm, red[w]);
+        scale_sh = fp8::scale_from_absmax_bits(mm);
+        scales[blockIdx.x] = scale_sh;
+    }
+    __syncthreads();
+    float inv = 1.f / scale_sh;
+    for (uint32_t g = 0; g < n_tensors; g++) {
+        const uint64_t src = tb.base[g] + off;
+        for (uint32_t sg = 0; sg < segs_per_tensor; sg++) {
+            const uint4* src4 = reinterpret_cast<const uint4*>(src + sg * src_stride);
+            uint2* dseg = dst + (static_cast<uint64_t>(g) * segs_per_tensor + sg) * n8;
+            for (uint64_t u = threadIdx.x; u < n8; u += blockDim.x) {
+                uint4 pk = src4[u];
+                const uint16_t* h = reinterpret_cast<const uint16_t*>(&pk);
+                uint8_t out[8];
+#pragma unroll
+                for (int i = 0; i < 8; i++) {
+                    float f = fp8::bits_f32(static_cast<uint32_t>(h[i]) << 16);
+                    out[i] = fp8::f32_to_e4m3(f * inv);
+                }
+                dseg[u] = *reinterpret_cast<const uint2*>(out);
+            }
+        }
+    }
+}
+
+__global__ void dequant_blocks_fp8_bf16_tset_kernel(const uint64_t* __restrict__ src_ptrs,
+                                                    const uint64_t* __restrict__ dst_offs,
+                                                    const float* __restrict__ scales,
+                                                    uint32_t n_tensors, uint32_t segs_per_tensor,
+                                                    uint64_t seg_elems, uint64_t dst_stride,
+                                                    TensorBases tb) {
+    const uint2* src = reinterpret_cast<const uint2*>(src_ptrs[blockIdx.x]);
+    const uint64_t off = dst_offs[blockIdx.x];
+    float scale = scales[blockIdx.x];
+    uint64_t n8 = seg_elems / 8;
+    for (uint32_t g = 0; g < n_tensors; g++) {
+        const uint64_t dst = tb.base[g] + off;
+        for (uint32_t sg = 0; sg < segs_per_tensor; sg++) {
+            const uint2* sseg = src + (static_cast<uint64_t>(g) * segs_per_tensor + sg) * n8;
+            uint4* dst4 = reinterpret_cast<uint4*>(dst + sg * dst_stride);
+            for (uint64_t u = threadIdx.x; u < n8; u += blockDim.x) {
+                uint2 pk = sseg[u];
+                const uint8_t* b = reinterpret_cast<const uint8_t*>(&pk);
+                uint16_t out[8];
+#pragma unroll
+                for (int i = 0; i < 8; i++) out[i] = fp8::decode_to_bf16(b[i], scale);
+                dst4[u] = *reinterpret_cast<const uint4*>(out);
+            }
+        }
+    }
+}
+
+// mxfp4: workgroup (b, s, chunk) as in the segmented kernels; the stored side
+// is indexed by the page-global unit s * (seg_elems / 8) + u with s counted
+// over ALL tensors, so later tensors' codes and scale bytes land where the
+// contiguous kernel puts them. The quad invariant holds inside every segment
+// as it does there (seg_elems % 32 == 0).
+__global__ void quant_blocks_bf16_mxfp4_tset_kernel(const uint64_t* __restrict__ src_offs,
+                                                    const uint64_t* __restrict__ dst_ptrs,
+                                                    uint32_t n_segments,
+                                                    uint32_t segs_per_tensor,
+                                                    uint32_t chunks_per_seg, uint64_t seg_elems,
+                                                    uint64_t src_stride, TensorBases tb) {
+    uint64_t sd[2];
+    uint32_t seg;
+    uint32_t chunk =
+        block_seg_chunk_descs(src_offs, dst_ptrs, n_segments, chunks_per_seg, sd, &seg);
+    uint32_t g = seg / segs_per_tensor;
+    uint32_t r = seg - g * segs_per_tensor;
+    uint64_t n8 = seg_elems / 8;
+    const uint4* src4 = reinterpret_cast<const uint4*>(tb.base[g] + sd[0] + r * src_stride);
+    uint32_t* codes = reinterpret_cast<uint32_t*>(sd[1]) + seg * n8;
+    uint8_t* scales =
+        reinterpret_cast<uint8_t*>(sd[1]) + n_segments * seg_elems / 2 + seg * (n8 >> 2);
+    uint64_t step = static_cast<uint64_t>(chunks_per_seg) * blockDim.x;
+    for (uint64_t u = static_cast<uint64_t>(chunk) * blockDim.x + threadIdx.x; u < n8;
+         u += step) {
+        uint4 pk = src4[u];
+        const uint16_t* h = reinterpret_cast<const uint16_t*>(&pk);
+        uint32_t key = 0;
+#pragma unroll
+        for (int i = 0; i < 8; i++) key = mxfp4::key_step(key, h[i]);
+        key = max(key, __shfl_xor(key, 1, 64));
+        key = max(key, __shfl_xor(key, 2, 64));
+        uint8_t E = mxfp4::group_exponent(key);
+        uint32_t out = 0;
+#pragma unroll
+        for (int i = 0; i < 8; i++)
+            out |= static_cast<uint32_t>(mxfp4::encode(h[i], E)) << (4 * i);
+        codes[u] = out;
+        if ((u & 3u) == 0) scales[u >> 2] = E;
+    }
+}
+
+__global__ void dequant_blocks_mxfp4_bf16_tset_kernel(const uint64_t* __restrict__ src_ptrs,
+                                                      const uint64_t* __restrict__ dst_offs,
+                                                      uint32_t n_segments,
+                                                      uint32_t segs_per_tensor,
+                                                      uint32_t chunks_per_seg,
+                                                      uint64_t seg_elems, uint64_t dst_stride,
+                                                      TensorBases tb) {
+    uint64_t sd[2];
+    uint32_t seg;
+    uint32_t chunk =
+        block_seg_chunk_descs(src_ptrs, dst_offs, n_segments, chunks_per_seg, sd, &seg);
+    uint32_t g = seg / segs_per_tensor;
+    uint32_t r = seg - g * segs_per_tensor;
+    uint64_t n8 = seg_elems / 8;
+    const uint32_t* codes = reinterpret_cast<const uint32_t*>(sd[0]) + seg * n8;
+    const uint8_t* scales =
+        reinterpret_cast<const uint8_t*>(sd[0]) + n_segments * seg_elems / 2 + seg * (n8 >> 2);
+    uint4* dst4 = reinterpret_cast<uint4*>(tb.base[g] + sd[1] + r * dst_stride);
+    uint64_t step = static_cast<uint64_t>(chunks_per_seg) * blockDim.x;
+    for (uint64_t u = static_cast<uint64_t>(chunk) * blockDim.x + threadIdx.x; u < n8;
+         u += step) {
+        uint32_t pk = codes[u];
+        uint8_t E = scales[u >> 2];  // the quad's four lanes read the same byte
+        uint16_t out[8];
+#pragma unroll
+        for (int i = 0; i < 8; i++)
+            out[i] = mxfp4::decode(static_cast<uint8_t>((pk >> (4 * i)) & 0xfu), E);
+        dst4[u] = *reinterpret_cast<const uint4*>(out);
+    }
+}
+
+// What both tensor-set launchers check and build first: the geometry, the
+// table itself, and whether every base keeps 16-byte alignment.
+static bool tset_table(const char* what, PageCodec codec, size_t page_bytes, PageSegments seg,
+                       TensorTable tset, TensorBases* tb, bool* bases16) {
+    if (!tensors_legal(codec, page_bytes, seg.n, seg.stride_bytes, tset.n) || !tset.bases) {
+        snprintf(g_err, sizeof(g_err), "%s: illegal tensor set geometry", what);
+        return false;
+    }
+    *bases16 = true;
+    memset(tb, 0, sizeof(*tb));
+    for (uint32_t g = 0; g < tset.n; g++) {
+        tb->base[g] = tset.bases[g];
+        if (tset.bases[g] % 16 != 0) *bases16 = false;
+    }
+    return true;
+}
+
+bool launch_copy_blocks_tset(int dev, Stream stream, const uint64_t* dev_src,
+                             const uint64_t* dev_dst, int n_blocks, size_t bytes_per_block,
+                             bool aligned16, PageSegments seg, PageDir dir, TensorTable tset) {
+    TensorBases tb;
+    bool bases16;
+    if (!tset_table("launch_copy_blocks_tset", PageCodec::kNone, bytes_per_block, seg, tset,
+                    &tb, &bases16))
+        return false;
+    if (n_blocks <= 0 || bytes_per_block == 0) return true;
+    const uint32_t per_tensor = seg.n / tset.n;
+    const uint64_t stride = per_tensor > 1 ? seg.stride_bytes : 0;
+    const uint64_t seg_bytes = bytes_per_block / seg.n;
+    const bool vec = aligned16 && bases16 && seg_bytes % 16 == 0 && stride % 16 == 0;
+    const uint64_t units = vec ? seg_bytes / 16 : seg_bytes;
+    const int threads = 512;  // as launch_copy_blocks
+    uint32_t chunks, grid;
+    if (!seg_grid(units, n_blocks, seg.n, threads, &chunks, &grid)) {
+        snprintf(g_err, sizeof(g_err), "launch_copy_blocks_tset: grid does not fit");
+        return false;
+    }
+    HIP_OK(hipSetDevice(dev));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const uint32_t to_pool = dir == PageDir::kStore;
+    if (vec)
+        hipLaunchKernelGGL(copy_blocks_vec_tset_kernel, dim3(grid), dim3(threads), 0, s, dev_src,
+                           dev_dst, seg.n, per_tensor, chunks, to_pool, units, stride, tb);
+    else
+        hipLaunchKernelGGL(copy_blocks_byte_tset_kernel, dim3(grid), dim3(threads), 0, s,
+                           dev_src, dev_dst, seg.n, per_tensor, chunks, to_pool, units, stride,
+                           tb);
+    HIP_OK(hipGetLastError());
+    return true;
+}
+
+bool launch_transform_blocks_tset(int dev, Stream stream, PageCodec codec, PageDir dir,
+                                  const uint64_t* dev_src, const uint64_t* dev_dst,
+                                  float* dev_scales, int n_blocks, size_t elems_per_block,
+                                  bool aligned16, PageSegments seg, TensorTable tset) {
+    const char* what = "launch_transform_blocks_tset";
+    TensorBases tb;
+    bool bases16;
+    if (!page_codec_transforms(codec) || elems_per_block == 0 ||
+        !page_legal(codec, elems_per_block * kPageElemBytes)) {
+        snprintf(g_err, sizeof(g_err), "%s: not a page of a transforming codec", what);
+        return false;
+    }
+    if (!tset_table(what, codec, elems_per_block * kPageElemBytes, seg, tset, &tb, &bases16))
+        return false;
+    if (!aligned16 || !bases16) {
+        snprintf(g_err, sizeof(g_err), "%s: %s needs 16-byte-aligned bases and offsets", what,
+                 page_codec_info(codec).name);
+        return false;
+    }
+    if (page_codec_info(codec).page_scale && !dev_scales) return false;
+    if (n_blocks <= 0) return true;
+    const uint32_t per_tensor = seg.n / tset.n;
+    const uint64_t stride = per_tensor > 1 ? seg.stride_bytes : 0;
+    const uint64_t seg_elems = elems_per_block / seg.n;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const bool store = dir == PageDir::kStore;
+    switch (codec) {
+        case PageCodec::kFp8:
+            HIP_OK(hipSetDevice(dev));
+            if (store)
+                hipLaunchKernelGGL(quant_blocks_bf16_fp8_tset_kernel, dim3(n_blocks), dim3(512),
+                                   0, s, dev_src, dev_dst, dev_scales, tset.n, per_tensor,
+                                   seg_elems, stride, tb);
+            else
+                hipLaunchKernelGGL(dequant_blocks_fp8_bf16_tset_kernel, dim3(n_blocks),
+                                   dim3(512), 0, s, dev_src, dev_dst, dev_scales, tset.n,
+                                   per_tensor, seg_elems, stride, tb);
+            break;
+        case PageCodec::kMxfp4: {
+            uint32_t chunks, grid;
+            if (!seg_grid(seg_elems / 8, n_blocks, seg.n, kMxfp4Threads, &chunks, &grid)) {
+                snprintf(g_err, sizeof(g_err), "%s: grid does not fit", what);
+                return false;
+            }
+            HIP_OK(hipSetDevice(dev));
+            if (store)
+                hipLaunchKernelGGL(quant_blocks_bf16_mxfp4_tset_kernel, dim3(grid),
+                                   dim3(kMxfp4Threads), 0, s, dev_src, dev_dst, seg.n,
+                                   per_tensor, chunks, seg_elems, stride, tb);
+            else
+                hipLaunchKernelGGL(dequant_blocks_mxfp4_bf16_tset_kernel, dim3(grid),
+                                   dim3(kMxfp4Threads), 0, s, dev_src, dev_dst, seg.n,
+                                   per_tensor, chunks, seg_elems, stride, tb);
+            break;
+        }
+        default:
+            return false;
+    }
+    HIP_OK(hipGetLastError());
+    return true;
+}
+
 // --- sliced reads --------------------------------------------------------------
 // From each stored block take n_pieces pieces, piece p at LOGICAL byte
 // offset + p * stride of the written page, and write their concatenation into

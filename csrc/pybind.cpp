@@ -328,6 +328,72 @@ std::vector<float> transform_blocks_seg_py(const char* what, int codec_id, PageD
     return scales;
 }
 
+// ---- tensor sets (docs/design.md, "tensor sets") -----------------------------
+// The two tensor-set launchers, called directly. The client side is `bases`
+// (one device address per tensor) plus one byte offset per block, the same in
+// every tensor; the pool side one pointer per block. Both return what the
+// launcher returns, so a refusal is False, not an exception; aligned16 is
+// computed from offsets and pool pointers as Shard::submit_copy does.
+// force_byte passes aligned16 = false, which selects the byte kernel for
+// aligned operands too.
+bool copy_blocks_tset_py(const std::vector<uint64_t>& bases, const std::vector<uint64_t>& offs,
+                         const std::vector<uint64_t>& pool, size_t bytes_per_block,
+                         uint32_t n_segments, uint64_t segment_stride, bool to_pool, int device,
+                         bool force_byte) {
+    const char* what = "_dbg_copy_blocks_tset";
+    require_gpu_and_pairs(what, offs, pool);
+    size_t n = offs.size();
+    if (n == 0) return true;
+    py::gil_scoped_release rel;
+    Pinned<uint64_t> h_client(n), h_pool(n);
+    memcpy(h_client.p, offs.data(), n * 8);
+    memcpy(h_pool.p, pool.data(), n * 8);
+    ScopedStream st(device);
+    bool ok = gpu::launch_copy_blocks_tset(
+        device, st.s, to_pool ? h_client.p : h_pool.p, to_pool ? h_pool.p : h_client.p,
+        static_cast<int>(n), bytes_per_block, !force_byte && all_aligned16(offs, pool),
+        PageSegments{n_segments, segment_stride}, to_pool ? PageDir::kStore : PageDir::kLoad,
+        gpu::TensorTable{bases.data(), static_cast<uint32_t>(bases.size())});
+    // Always drain the stream before the pinned descriptors go away.
+    if (!gpu::stream_sync(st.s))
+        throw std::runtime_error(std::string(what) + " failed: " + gpu::last_error());
+    return ok;
+}
+
+// to_pool quantizes (the scales come back), else dequantizes (they go in).
+std::pair<bool, std::vector<float>> transform_blocks_tset_py(
+    int codec_id, bool to_pool, const std::vector<uint64_t>& bases,
+    const std::vector<uint64_t>& offs, const std::vector<uint64_t>& pool,
+    std::vector<float> scales, size_t elems_per_block, uint32_t n_segments,
+    uint64_t segment_stride, int device) {
+    const char* what = "_dbg_transform_blocks_tset";
+    const PageCodec codec = codec_from_id(what, codec_id);
+    require_gpu_and_pairs(what, offs, pool);
+    size_t n = offs.size();
+    const bool page_scale = page_codec_info(codec).page_scale;
+    if (page_scale && !to_pool && scales.size() != n)
+        throw std::invalid_argument(std::string(what) + ": one scale per block");
+    scales.resize(page_scale ? n : 0);
+    if (n == 0) return {true, scales};
+    py::gil_scoped_release rel;
+    Pinned<uint64_t> h_client(n), h_pool(n);
+    Pinned<float> h_scale(n);
+    memcpy(h_client.p, offs.data(), n * 8);
+    memcpy(h_pool.p, pool.data(), n * 8);
+    memcpy(h_scale.p, scales.data(), scales.size() * sizeof(float));
+    ScopedStream st(device);
+    bool ok = gpu::launch_transform_blocks_tset(
+        device, st.s, codec, to_pool ? PageDir::kStore : PageDir::kLoad,
+        to_pool ? h_client.p : h_pool.p, to_pool ? h_pool.p : h_client.p, h_scale.p,
+        static_cast<int>(n), elems_per_block, all_aligned16(offs, pool),
+        PageSegments{n_segments, segment_stride},
+        gpu::TensorTable{bases.data(), static_cast<uint32_t>(bases.size())});
+    if (!gpu::stream_sync(st.s))
+        throw std::runtime_error(std::string(what) + " failed: " + gpu::last_error());
+    if (ok) memcpy(scales.data(), h_scale.p, scales.size() * sizeof(float));
+    return {ok, scales};
+}
+
 // ---- sliced reads (docs/design.md, "sliced reads") ---------------------------
 // A slice from Python: None, or (n_pieces, page, offset, piece, stride) in
 // units of `unit` bytes (the tensor's element size; 1 for the byte-level
@@ -448,13 +514,18 @@ struct ShardRun {
 };
 
 // slices (null for _dbg_shard_run): one entry per copy job, None or the job's
-// slice in bytes as slice_from_py takes it.
+// slice in bytes as slice_from_py takes it. tsets (null but for
+// _dbg_shard_run_tset): one entry per copy job, None or (bases,
+// segs_per_tensor); the job's client-side descriptors are then byte offsets.
 py::tuple shard_run_impl(const char* what, int device, int n_streams, int slots_per_stream,
                          size_t max_descs_per_slot, const py::list& copy_jobs,
                          const py::list& fabric_jobs, int n_threads, double timeout_s,
-                         const py::list* slices) {
+                         const py::list* slices, const py::list* tsets = nullptr) {
     if (slices && slices->size() != copy_jobs.size())
         throw std::invalid_argument(std::string(what) + ": one slice (or None) per copy job");
+    if (tsets && tsets->size() != copy_jobs.size())
+        throw std::invalid_argument(std::string(what) +
+                                    ": one tensor set (or None) per copy job");
     if (device < -1) throw std::invalid_argument(std::string(what) + ": device is -1 or an ordinal");
     if (device >= 0 && (!gpu::available() || device >= gpu::device_count()))
         throw std::runtime_error(std::string(what) + ": no such GPU available");
@@ -485,6 +556,15 @@ py::tuple shard_run_impl(const char* what, int device, int n_streams, int slots_
             j.scales = std::make_shared<std::vector<float>>(t[7].cast<std::vector<float>>());
         j.scales_off = t[8].cast<size_t>();
         if (slices) j.slice = slice_from_py(what, (*slices)[i], 1);
+        if (tsets && !py::object((*tsets)[i]).is_none()) {
+            py::tuple ts = (*tsets)[i].cast<py::tuple>();
+            if (ts.size() != 2)
+                throw std::invalid_argument(std::string(what) +
+                                            ": a tensor set is (bases, segs_per_tensor)");
+            j.tensor_bases = std::make_shared<const std::vector<uint64_t>>(
+                ts[0].cast<std::vector<uint64_t>>());
+            j.segs_per_tensor = ts[1].cast<uint32_t>();
+        }
         j.done = [run, i](bool ok) { run->on_done(i, ok); };
         st->scales.push_back(j.scales);
         st->copy_jobs.push_back(std::move(j));
@@ -815,6 +895,47 @@ PYBIND11_MODULE(_native, m) {
             py::arg("block_size"), py::arg("ptr"), py::arg("device"),
             py::arg("n_segments") = 1, py::arg("segment_stride") = 0,
             py::arg("page_slice") = py::none())
+        .def(
+            "rw_tset_blob",
+            [](ClientConn& c, const std::string& op, py::buffer blob, py::buffer offsets,
+               uint64_t element_size, int block_size, uint32_t set_id, uint32_t n_tensors,
+               int device, bool sync_response, uint32_t extra_flags, uint32_t n_segments,
+               uint64_t segment_stride, bool ticketed) {
+                // rw_local_blob over a registered tensor set: offsets (in
+                // elements) are relative to every tensor of the set and
+                // n_segments is the total over all tensors. ticketed: as
+                // rw_local_blob_async. Returns (status, ticket).
+                py::buffer_info bb = blob.request();
+                py::buffer_info ob = offsets.request();
+                if (ob.itemsize != 8) throw std::runtime_error("offsets must be uint64[n]");
+                size_t n = static_cast<size_t>(ob.size);
+                const uint64_t* offs = static_cast<const uint64_t*>(ob.ptr);
+                std::vector<uint64_t> byte_offs(n);
+                for (size_t i = 0; i < n; i++) byte_offs[i] = offs[i] * element_size;
+                const char* bp = static_cast<const char*>(bb.ptr);
+                size_t blen = static_cast<size_t>(bb.size) * bb.itemsize;
+                const PackedLocalTensorExt ts{set_id, n_tensors, 0};
+                uint64_t ticket = 0;
+                int ret;
+                {
+                    py::gil_scoped_release rel;
+                    ret = c.rw_local_packed(op.empty() ? 'W' : op[0], bp, blen, byte_offs.data(),
+                                            n, block_size, 0, device, sync_response || ticketed,
+                                            ticketed ? &ticket : nullptr, extra_flags,
+                                            n_segments, segment_stride * element_size, nullptr,
+                                            &ts);
+                }
+                return py::make_tuple(ret, ticket);
+            },
+            py::arg("op"), py::arg("blob"), py::arg("offsets"), py::arg("element_size"),
+            py::arg("block_size"), py::arg("set_id"), py::arg("n_tensors"), py::arg("device"),
+            py::arg("sync_response") = false, py::arg("extra_flags") = 0,
+            py::arg("n_segments") = 1, py::arg("segment_stride") = 0,
+            py::arg("ticketed") = false)
+        .def("register_tensor_set", &ClientConn::register_tensor_set, py::arg("ptrs"),
+             py::arg("extents"), py::arg("device"), py::call_guard<py::gil_scoped_release>())
+        .def("release_tensor_set", &ClientConn::release_tensor_set, py::arg("set_id"),
+             py::call_guard<py::gil_scoped_release>())
         .def("wait_local_ticket", &ClientConn::wait_local_ticket,
              py::call_guard<py::gil_scoped_release>())
         .def("sync_local", &ClientConn::sync_local, py::call_guard<py::gil_scoped_release>())
@@ -1002,6 +1123,27 @@ PYBIND11_MODULE(_native, m) {
           py::arg("codec"), py::arg("page_bytes"), py::arg("n_segments"),
           py::arg("stride_bytes"));
     m.attr("_MAX_PAGE_SEGMENTS") = kMaxPageSegments;
+    // The tensor-set predicate; n_segments is the total over all tensors.
+    m.def("_dbg_tensors_legal",
+          [](int codec, size_t page_bytes, uint64_t n_segments, uint64_t stride_bytes,
+             uint64_t n_tensors) {
+              return tensors_legal(codec_from_id("_dbg_tensors_legal", codec), page_bytes,
+                                   n_segments, stride_bytes, n_tensors);
+          },
+          py::arg("codec"), py::arg("page_bytes"), py::arg("n_segments"),
+          py::arg("stride_bytes"), py::arg("n_tensors"));
+    m.attr("_MAX_PAGE_TENSORS") = kMaxPageTensors;
+    // The tensor-set launchers (gpu.h), called directly: tensor bases, one
+    // client byte offset and one pool pointer per block. Return False for
+    // what the launcher refuses; the transform form returns (ok, scales).
+    m.def("_dbg_copy_blocks_tset", &copy_blocks_tset_py, py::arg("bases"),
+          py::arg("client_offsets"), py::arg("pool_ptrs"), py::arg("bytes_per_block"),
+          py::arg("n_segments"), py::arg("segment_stride"), py::arg("to_pool"),
+          py::arg("device") = 0, py::arg("force_byte") = false);
+    m.def("_dbg_transform_blocks_tset", &transform_blocks_tset_py, py::arg("codec"),
+          py::arg("to_pool"), py::arg("bases"), py::arg("client_offsets"),
+          py::arg("pool_ptrs"), py::arg("scales"), py::arg("elems_per_block"),
+          py::arg("n_segments"), py::arg("segment_stride"), py::arg("device") = 0);
     // The slice-geometry predicate; the slice is (n_pieces, page_bytes, offset,
     // piece_bytes, stride) in bytes, the client segments as above.
     m.def("_dbg_slice_legal",
@@ -1035,6 +1177,24 @@ PYBIND11_MODULE(_native, m) {
           py::arg("device"), py::arg("n_streams"), py::arg("slots_per_stream"),
           py::arg("max_descs_per_slot"), py::arg("copy_jobs"), py::arg("slices"),
           py::arg("n_threads"), py::arg("timeout_s"));
+    // _dbg_shard_run's copy jobs, each over a tensor set (or None) from
+    // `tsets`: (bases, segs_per_tensor), the client side being offsets.
+    // `slices` as for _dbg_shard_run_sliced (a set with a slice is refused).
+    m.def("_dbg_shard_run_tset",
+          [](int device, int n_streams, int slots_per_stream, size_t max_descs_per_slot,
+             const py::list& copy_jobs, const py::list& tsets, int n_threads,
+             double timeout_s, const py::object& slices) -> py::object {
+              py::list sl;
+              if (!slices.is_none()) sl = slices.cast<py::list>();
+              py::tuple out = shard_run_impl("_dbg_shard_run_tset", device, n_streams,
+                                             slots_per_stream, max_descs_per_slot, copy_jobs,
+                                             py::list(), n_threads, timeout_s,
+                                             slices.is_none() ? nullptr : &sl, &tsets);
+              return out[0];
+          },
+          py::arg("device"), py::arg("n_streams"), py::arg("slots_per_stream"),
+          py::arg("max_descs_per_slot"), py::arg("copy_jobs"), py::arg("tsets"),
+          py::arg("n_threads"), py::arg("timeout_s"), py::arg("slices") = py::none());
     // Jobs through a real Shard at small limits. A copy job is (src_ptrs,
     // dst_ptrs, bytes_per_block, codec_id, store, n_segments, segment_stride,
     // scales or None, scales_off), a fabric job (is_put, host buffer,
@@ -1055,9 +1215,21 @@ PYBIND11_MODULE(_native, m) {
           [](int device, int pid, uint64_t base_ptr, uint64_t base_offset, uint32_t block_size,
              uint32_t flags, uint32_t alloc_mb, py::bytes ipc,
              const std::vector<uint64_t>& offsets, const std::vector<std::string>& keys,
-             uint32_t n_segments, uint64_t segment_stride, const py::object& slice) {
+             uint32_t n_segments, uint64_t segment_stride, const py::object& slice,
+             const py::object& tensor_set) {
               const PackedLocalSliceExt sl =
                   slice_to_wire(slice_from_py("_dbg_build_packed_local", slice, 1));
+              // None, or (set_id, n_tensors[, rsvd])
+              PackedLocalTensorExt ts{};
+              if (!tensor_set.is_none()) {
+                  py::tuple t = tensor_set.cast<py::tuple>();
+                  if (t.size() != 2 && t.size() != 3)
+                      throw std::invalid_argument(
+                          "_dbg_build_packed_local: a tensor set is (set_id, n_tensors)");
+                  ts.set_id = t[0].cast<uint32_t>();
+                  ts.n_tensors = t[1].cast<uint32_t>();
+                  ts.rsvd = t.size() == 3 ? t[2].cast<uint64_t>() : 0;
+              }
               std::string ipc_s = ipc;
               if (ipc_s.size() != 64)
                   throw std::invalid_argument("_dbg_build_packed_local: ipc is 64 bytes");
@@ -1079,13 +1251,15 @@ PYBIND11_MODULE(_native, m) {
                   blob.append(keys[i]);
               }
               auto v = build_packed_local(h, n_segments, segment_stride, offsets.data(),
-                                          blob.data(), blob.size(), &sl);
+                                          blob.data(), blob.size(), &sl,
+                                          tensor_set.is_none() ? nullptr : &ts);
               return py::bytes(reinterpret_cast<const char*>(v.data()), v.size());
           },
           py::arg("device"), py::arg("pid"), py::arg("base_ptr"), py::arg("base_offset"),
           py::arg("block_size"), py::arg("flags"), py::arg("alloc_mb"), py::arg("ipc"),
           py::arg("offsets"), py::arg("keys"), py::arg("n_segments") = 1,
-          py::arg("segment_stride") = 0, py::arg("slice") = py::none());
+          py::arg("segment_stride") = 0, py::arg("slice") = py::none(),
+          py::arg("tensor_set") = py::none());
     m.def("_dbg_parse_packed_local", [](const std::string& op, py::bytes data) {
         std::string s = data;
         PackedLocalReq r;
@@ -1109,6 +1283,11 @@ PYBIND11_MODULE(_native, m) {
                                         r.slice.piece_bytes, r.slice.stride);
         else
             d["slice"] = py::none();
+        // None, or (set_id, n_tensors)
+        if (r.has_tset)
+            d["tensor_set"] = py::make_tuple(r.tset.set_id, r.tset.n_tensors);
+        else
+            d["tensor_set"] = py::none();
         py::list offs, keys;
         for (auto& [key, off] : r.blocks) {
             offs.append(off);

@@ -541,6 +541,9 @@ bool parse_packed_local(char op, const uint8_t* body, size_t body_len, Server::L
     v->n_segments = req.n_segments;
     v->segment_stride = req.segment_stride;
     v->slice = slice_from_wire(req.slice);
+    v->has_tset = req.has_tset;
+    v->tset_id = req.tset.set_id;
+    v->tset_n = req.tset.n_tensors;
     v->ipc = body + offsetof(PackedLocalHdr, ipc);
     v->ipc_len = 64;
     v->blocks = std::move(req.blocks);
@@ -595,6 +598,10 @@ void Server::handle_request(Conn* c, char op, std::vector<uint8_t> body) {
             return op_sync(c, ReqCtx{});
         case OP_SHM_SETUP:
             return op_shm_setup(c, body);
+        case OP_TSET_REGISTER:
+            return op_tset_register(c, body);
+        case OP_TSET_RELEASE:
+            return op_tset_release(c, body);
         case OP_RDMA_EXCHANGE:
             return op_exchange(c, body);
         case OP_RDMA_ALLOCATE: {
@@ -681,39 +688,94 @@ namespace {
 // Resolve the client's allocation base: same-process fast path (an IPC
 // handle cannot be opened inside the exporting process) or the per-conn
 // cached hipIpcOpenMemHandle mapping.
-void* resolve_client_base(Server::Conn* c, const Server::LocalView& msg) {
-    if (msg.pid != 0 && msg.pid == static_cast<int32_t>(getpid()) && msg.base_ptr != 0)
-        return reinterpret_cast<void*>(msg.base_ptr);
-    // dmabuf IPC limitation on this ROCm/driver stack: hipIpcOpenMemHandle
-    // HANGS FOREVER importing allocations >= 2 GiB (bisected by
-    // scripts/ipc_size_probe.py: 1.5 GiB fine, 2.0 GiB hangs). Refuse
-    // instead of wedging this conn's poller/worker thread. Clients see a
-    // clear error and can split tensors (< 2 GiB per allocation, e.g.
-    // per-layer KV pools) or use the fabric path for the big tensor.
-    if (msg.alloc_mb >= 2048) {
-        ERROR("refusing IPC import of a %u MB client allocation: "
-              "hipIpcOpenMemHandle hangs for >= 2 GiB allocations under "
-              "dmabuf IPC; split the tensor or use the fabric path",
-              msg.alloc_mb);
-        return nullptr;
-    }
-    std::vector<uint8_t> key(msg.ipc, msg.ipc + msg.ipc_len);
-    std::lock_guard<std::mutex> lk(c->ipc_mu);
+//
+// open_mapping_locked is the cached part, shared with tensor-set registration
+// (c->ipc_mu held): each distinct handle is opened once per connection.
+void* open_mapping_locked(Server::Conn* c, const uint8_t* ipc, int device) {
+    std::vector<uint8_t> key(ipc, ipc + gpu::kIpcHandleSize);
     auto it = c->ipc_cache.find(key);
     if (it != c->ipc_cache.end()) return it->second.first;
     // Bound the cache: a client that churns tensors would otherwise pin
     // every old allocation via its stale mapping. Only flush when nothing
-    // is in flight (a mapping may be read by a queued kernel).
-    if (c->ipc_cache.size() >= 64 && c->remain.load() == 0 &&
+    // is in flight (a mapping may be read by a queued kernel). Mappings that
+    // a live tensor set uses are neither counted nor closed.
+    if (c->ipc_cache.size() >= 64 + c->ipc_set_refs.size() && c->remain.load() == 0 &&
         c->fabric_inflight.load() == 0 && c->ipc_pin.load() == 1) {
-        for (auto& kv2 : c->ipc_cache) gpu::ipc_close(kv2.second.first);
-        c->ipc_cache.clear();
+        for (auto kv = c->ipc_cache.begin(); kv != c->ipc_cache.end();) {
+            if (c->ipc_set_refs.count(kv->second.first)) {
+                ++kv;
+                continue;
+            }
+            gpu::ipc_close(kv->second.first);
+            kv = c->ipc_cache.erase(kv);
+        }
     }
     gpu::IpcHandle h;
-    memcpy(h.bytes, msg.ipc, gpu::kIpcHandleSize);
-    void* base = gpu::ipc_open(h, msg.device);
-    if (base) c->ipc_cache.emplace(std::move(key), std::make_pair(base, msg.device));
+    memcpy(h.bytes, ipc, gpu::kIpcHandleSize);
+    void* base = gpu::ipc_open(h, device);
+    if (base) c->ipc_cache.emplace(std::move(key), std::make_pair(base, device));
     return base;
+}
+
+// dmabuf IPC limitation on this ROCm/driver stack: hipIpcOpenMemHandle
+// HANGS FOREVER importing allocations >= 2 GiB (bisected by
+// scripts/ipc_size_probe.py: 1.5 GiB fine, 2.0 GiB hangs). Refuse
+// instead of wedging this conn's poller/worker thread. Clients see a
+// clear error and can split tensors (< 2 GiB per allocation, e.g.
+// per-layer KV pools) or use the fabric path for the big tensor.
+bool import_size_ok(uint32_t alloc_mb) {
+    if (alloc_mb < 2048) return true;
+    ERROR("refusing IPC import of a %u MB client allocation: "
+          "hipIpcOpenMemHandle hangs for >= 2 GiB allocations under "
+          "dmabuf IPC; split the tensor or use the fabric path",
+          alloc_mb);
+    return false;
+}
+
+void* resolve_client_base(Server::Conn* c, const Server::LocalView& msg) {
+    if (msg.pid != 0 && msg.pid == static_cast<int32_t>(getpid()) && msg.base_ptr != 0)
+        return reinterpret_cast<void*>(msg.base_ptr);
+    if (!import_size_ok(msg.alloc_mb)) return nullptr;
+    std::lock_guard<std::mutex> lk(c->ipc_mu);
+    return open_mapping_locked(c, msg.ipc, msg.device);
+}
+
+// The registered set a request names, or null (INVALID_REQ) for an unknown or
+// released id or a tensor count that is not the registered one.
+std::shared_ptr<const Server::Conn::TensorSet> find_tensor_set(Server::Conn* c,
+                                                               const Server::LocalView& msg) {
+    std::lock_guard<std::mutex> lk(c->ipc_mu);
+    auto it = c->tsets.find(msg.tset_id);
+    if (it == c->tsets.end() || it->second->bases->size() != msg.tset_n ||
+        it->second->device != msg.device)
+        return nullptr;
+    return it->second;
+}
+
+// What a request over a tensor set must satisfy beyond the parser's checks:
+// the geometry under `codec`, every page part inside the smallest tensor's
+// registered extent, and for a transforming codec aligned bases and offsets.
+bool tensor_set_request_ok(const Server::Conn::TensorSet& ts, const Server::LocalView& msg,
+                           PageCodec codec) {
+    const size_t page = static_cast<size_t>(msg.block_size);
+    if (!tensors_legal(codec, page, msg.n_segments, msg.segment_stride, ts.bases->size()))
+        return false;
+    const uint64_t per = msg.n_segments / ts.bases->size();
+    const uint64_t seg = page / msg.n_segments;
+    // last byte of a part: offs + (per - 1) * stride + seg, without overflow
+    uint64_t span = seg;
+    if (per > 1) {
+        if (msg.segment_stride > (UINT64_MAX - seg) / (per - 1)) return false;
+        span += (per - 1) * msg.segment_stride;
+    }
+    if (span > ts.min_extent) return false;
+    const bool transforms = page_codec_transforms(codec);
+    if (transforms && !ts.bases16) return false;
+    for (auto& b : msg.blocks) {
+        if (b.second > ts.min_extent - span) return false;
+        if (transforms && b.second % 16 != 0) return false;
+    }
+    return true;
 }
 
 // Holds Conn::ipc_pin for a handler's resolve→enqueue window so a concurrent
@@ -733,9 +795,19 @@ void Server::op_local_write(Conn* c, const LocalView& msg, const ReqCtx& ctx) {
     if (msg.ipc_len != gpu::kIpcHandleSize || msg.block_size <= 0)
         return reply_local(c, ctx, INVALID_REQ);
     IpcPinGuard pin(c);
-    void* base = resolve_client_base(c, msg);
-    if (!base) return reply_local(c, ctx, INTERNAL_ERROR);
-    uint8_t* client_ptr = static_cast<uint8_t*>(base) + msg.base_offset;
+    // Over a tensor set the block offsets are the client descriptors
+    // themselves (relative to every tensor's base): there is no single base.
+    std::shared_ptr<const Conn::TensorSet> tset;
+    uint8_t* client_ptr = nullptr;
+    if (msg.has_tset) {
+        tset = find_tensor_set(c, msg);
+        if (!tset) return reply_local(c, ctx, INVALID_REQ);
+    } else {
+        void* base = resolve_client_base(c, msg);
+        if (!base) return reply_local(c, ctx, INTERNAL_ERROR);
+        client_ptr = static_cast<uint8_t*>(base) + msg.base_offset;
+    }
+    const uintptr_t client_addr = reinterpret_cast<uintptr_t>(client_ptr);
 
     Shard* shard = shard_for_device(msg.device);
     size_t page = static_cast<size_t>(msg.block_size);
@@ -747,14 +819,19 @@ void Server::op_local_write(Conn* c, const LocalView& msg, const ReqCtx& ctx) {
     if (!page_legal(codec, page)) return reply_local(c, ctx, INVALID_REQ);
     // Segmented source pages: the geometry rules, the stride's alignment for
     // transforming codecs among them, are segments_legal's.
-    if (!segments_legal(codec, page, msg.n_segments, msg.segment_stride))
+    if (tset) {
+        // tensors_legal, every part inside its tensor, aligned bases and
+        // offsets for a transforming codec.
+        if (!tensor_set_request_ok(*tset, msg, codec)) return reply_local(c, ctx, INVALID_REQ);
+    } else if (!segments_legal(codec, page, msg.n_segments, msg.segment_stride)) {
         return reply_local(c, ctx, INVALID_REQ);
+    }
     // The quantize kernels load 16 bytes per lane: every source page must
     // start 16-byte aligned (pool blocks always do), and a 16-byte stride
     // then keeps every segment aligned.
-    if (page_codec_transforms(codec)) {
+    if (page_codec_transforms(codec) && !tset) {
         for (size_t i = 0; i < nb; i++)
-            if (reinterpret_cast<uintptr_t>(client_ptr + msg.blocks[i].second) % 16 != 0)
+            if ((client_addr + msg.blocks[i].second) % 16 != 0)
                 return reply_local(c, ctx, INVALID_REQ);
     }
     const size_t stored = stored_bytes(codec, page);
@@ -828,6 +905,10 @@ void Server::op_local_write(Conn* c, const LocalView& msg, const ReqCtx& ctx) {
     job.dir = PageDir::kStore;
     job.n_segments = msg.n_segments;
     job.segment_stride = msg.segment_stride;
+    if (tset) {
+        job.tensor_bases = tset->bases;
+        job.segs_per_tensor = msg.n_segments / static_cast<uint32_t>(tset->bases->size());
+    }
     job.scales = scales_out;
     for (size_t i = 0; i < n_fresh; i++) {
         auto* e = slab_batch.make();
@@ -840,8 +921,7 @@ void Server::op_local_write(Conn* c, const LocalView& msg, const ReqCtx& ctx) {
         e->born_sec = KvIndex::now_sec();
         e->last_access.store(t, std::memory_order_relaxed);
         entries->emplace_back(e);
-        job.src.push_back(
-            reinterpret_cast<uint64_t>(client_ptr + msg.blocks[fresh[i]].second));
+        job.src.push_back(client_addr + msg.blocks[fresh[i]].second);
         job.dst.push_back(reinterpret_cast<uint64_t>(slots[i].first));
     }
     maybe_extend(shard);
@@ -947,15 +1027,32 @@ void Server::op_local_read(Conn* c, const LocalView& msg, const ReqCtx& ctx) {
     if (msg.ipc_len != gpu::kIpcHandleSize || msg.block_size <= 0)
         return reply_local(c, ctx, INVALID_REQ);
     IpcPinGuard pin(c);
-    void* base = resolve_client_base(c, msg);
-    if (!base) return reply_local(c, ctx, INTERNAL_ERROR);
-    uint8_t* client_ptr = static_cast<uint8_t*>(base) + msg.base_offset;
+    // Over a tensor set the block offsets are the client descriptors
+    // themselves, as in op_local_write.
+    std::shared_ptr<const Conn::TensorSet> tset;
+    uint8_t* client_ptr = nullptr;
+    if (msg.has_tset) {
+        tset = find_tensor_set(c, msg);
+        if (!tset || slice_is_set(msg.slice)) return reply_local(c, ctx, INVALID_REQ);
+    } else {
+        void* base = resolve_client_base(c, msg);
+        if (!base) return reply_local(c, ctx, INTERNAL_ERROR);
+        client_ptr = static_cast<uint8_t*>(base) + msg.base_offset;
+    }
+    const uintptr_t client_addr = reinterpret_cast<uintptr_t>(client_ptr);
     size_t page = static_cast<size_t>(msg.block_size);
     // Segmented destination pages. Plain rules here; a compressed entry is
     // checked against its own codec's rules in the sweep, next to
     // stored_matches.
-    if (!segments_legal(PageCodec::kNone, page, msg.n_segments, msg.segment_stride))
+    if (tset) {
+        if (!tensor_set_request_ok(*tset, msg, PageCodec::kNone))
+            return reply_local(c, ctx, INVALID_REQ);
+    } else if (!segments_legal(PageCodec::kNone, page, msg.n_segments, msg.segment_stride)) {
         return reply_local(c, ctx, INVALID_REQ);
+    }
+    // A request sees entries of at most a few codecs: each is checked once.
+    bool tset_codec_ok[kNumPageCodecs] = {true};
+    bool tset_codec_seen[kNumPageCodecs] = {true};
     // Sliced read: `page` is the sliced page (what the client receives); the
     // stored pages are slice.page_bytes. Plain rules here too, as in the
     // parser; the sweep checks every entry against its own codec.
@@ -1019,8 +1116,21 @@ void Server::op_local_read(Conn* c, const LocalView& msg, const ReqCtx& ctx) {
                 // 16-byte-aligned client address as below.
                 if (!stored_matches(e->codec, e->size, msg.slice.page_bytes) ||
                     !slice_legal(e->codec, msg.slice, client_seg) ||
-                    (page_codec_transforms(e->codec) &&
-                     reinterpret_cast<uintptr_t>(client_ptr + b.second) % 16 != 0)) {
+                    (page_codec_transforms(e->codec) && (client_addr + b.second) % 16 != 0)) {
+                    err = INVALID_REQ;
+                    return false;
+                }
+            } else if (tset) {
+                // The whole request against the entry's codec (geometry,
+                // aligned bases and offsets), once per codec; the page must
+                // be the written size, for plain entries too: a smaller
+                // stored block would be read past its end.
+                const size_t ci = static_cast<size_t>(e->codec);
+                if (!tset_codec_seen[ci]) {
+                    tset_codec_seen[ci] = true;
+                    tset_codec_ok[ci] = tensor_set_request_ok(*tset, msg, e->codec);
+                }
+                if (!tset_codec_ok[ci] || !stored_matches(e->codec, e->size, page)) {
                     err = INVALID_REQ;
                     return false;
                 }
@@ -1029,7 +1139,7 @@ void Server::op_local_read(Conn* c, const LocalView& msg, const ReqCtx& ctx) {
                        // and the dequantize kernels store 16 bytes per lane
                        // into the client.
                        (!stored_matches(e->codec, e->size, page) ||
-                        reinterpret_cast<uintptr_t>(client_ptr + b.second) % 16 != 0 ||
+                        (client_addr + b.second) % 16 != 0 ||
                         !segments_legal(e->codec, page, msg.n_segments, msg.segment_stride))) {
                 err = INVALID_REQ;
                 return false;
@@ -1047,6 +1157,11 @@ void Server::op_local_read(Conn* c, const LocalView& msg, const ReqCtx& ctx) {
                     it->second.n_segments = msg.n_segments;
                     it->second.segment_stride = msg.segment_stride;
                     it->second.slice = msg.slice;
+                    if (tset) {
+                        it->second.tensor_bases = tset->bases;
+                        it->second.segs_per_tensor =
+                            msg.n_segments / static_cast<uint32_t>(tset->bases->size());
+                    }
                     if (page_codec_info(e->codec).page_scale)
                         it->second.scales = std::make_shared<std::vector<float>>();
                 }
@@ -1056,7 +1171,7 @@ void Server::op_local_read(Conn* c, const LocalView& msg, const ReqCtx& ctx) {
             Shard::CopyJob& job = *last_job;
             if (job.scales) job.scales->push_back(e->scale);
             job.src.push_back(reinterpret_cast<uint64_t>(e->ptr));
-            job.dst.push_back(reinterpret_cast<uint64_t>(client_ptr + b.second));
+            job.dst.push_back(client_addr + b.second);
             held->push_back(*v);
             return true;
         });
@@ -1111,6 +1226,78 @@ void Server::op_local_read(Conn* c, const LocalView& msg, const ReqCtx& ctx) {
         fprintf(stderr, "[rdbg] read n=%zu collect=%.0f submit=%.0f\n", msg.blocks.size(),
                 us(tr0, tcol), us(tcol, Clock::now()));
     if (!sync_resp && !ctx.shm) send_status(c, TASK_ACCEPTED);
+}
+
+// Register a tensor set (socket only; docs/design.md, "tensor sets"). Every
+// record is resolved like a request's base: the same-process fast path, or the
+// connection's mapping cache, so each distinct handle is opened once. The
+// mappings a set uses are counted in ipc_set_refs as they are resolved, which
+// keeps a cache flush triggered by a later record from closing them.
+void Server::op_tset_register(Conn* c, const std::vector<uint8_t>& body) {
+    PackedTensorSetHdr hdr;
+    std::vector<PackedTensorRec> recs;
+    if (!parse_tensor_set(body.data(), body.size(), &hdr, &recs))
+        return send_status(c, INVALID_REQ);
+    if (!gpu::available()) return send_status(c, SYSTEM_ERROR);
+    const bool same_process = hdr.pid != 0 && hdr.pid == static_cast<int32_t>(getpid());
+    for (const PackedTensorRec& r : recs)
+        if (r.extent_bytes == 0 || (same_process ? r.base_ptr == 0 : !import_size_ok(r.alloc_mb)))
+            return send_status(c, INVALID_REQ);
+    IpcPinGuard pin(c);
+    auto set = std::make_shared<Conn::TensorSet>();
+    auto bases = std::make_shared<std::vector<uint64_t>>();
+    set->device = hdr.device;
+    set->min_extent = UINT64_MAX;
+    set->bases16 = true;
+    uint32_t id = 0;
+    {
+        std::lock_guard<std::mutex> lk(c->ipc_mu);
+        if (c->tsets.size() >= kMaxTensorSetsPerConn) return send_status(c, INVALID_REQ);
+        bool ok = true;
+        for (const PackedTensorRec& r : recs) {
+            uint64_t base = r.base_ptr;
+            if (!same_process) {
+                void* m = open_mapping_locked(c, r.ipc, hdr.device);
+                if (!m) {
+                    ok = false;
+                    break;
+                }
+                if (std::find(set->mappings.begin(), set->mappings.end(), m) ==
+                    set->mappings.end()) {
+                    set->mappings.push_back(m);
+                    c->ipc_set_refs[m]++;
+                }
+                base = reinterpret_cast<uint64_t>(m);
+            }
+            bases->push_back(base + r.base_offset);
+            if (bases->back() % 16 != 0) set->bases16 = false;
+            set->min_extent = std::min(set->min_extent, r.extent_bytes);
+        }
+        if (!ok) {
+            for (void* m : set->mappings)
+                if (--c->ipc_set_refs[m] == 0) c->ipc_set_refs.erase(m);
+            return send_status(c, INTERNAL_ERROR);
+        }
+        set->bases = std::move(bases);
+        id = c->next_tset_id++;
+        c->tsets.emplace(id, std::move(set));
+    }
+    send_status_raw(c, FINISH, &id, sizeof(id));
+}
+
+// Release a set: its id becomes unknown at once; its mappings stay in the
+// cache, open to the next flush. A job in flight keeps the bases it copied.
+void Server::op_tset_release(Conn* c, const std::vector<uint8_t>& body) {
+    uint32_t id = 0;
+    if (body.size() != sizeof(id)) return send_status(c, INVALID_REQ);
+    memcpy(&id, body.data(), sizeof(id));
+    std::lock_guard<std::mutex> lk(c->ipc_mu);
+    auto it = c->tsets.find(id);
+    if (it == c->tsets.end()) return send_status(c, INVALID_REQ);
+    for (void* m : it->second->mappings)
+        if (--c->ipc_set_refs[m] == 0) c->ipc_set_refs.erase(m);
+    c->tsets.erase(it);
+    send_status(c, FINISH);
 }
 
 void Server::op_sync(Conn* c, const ReqCtx& ctx) {

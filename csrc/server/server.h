@@ -149,6 +149,12 @@ class Server {
         // Sliced reads (OP_R_FAST only): slice.n != 0 asks for strided pieces
         // of every stored page; block_size is then the sliced page.
         PageSlice slice;
+        // Tensor sets (packed ops only): the pages span the tensors of the
+        // registered set tset_id; ipc, base_ptr and base_offset are ignored
+        // and the block offsets are relative to each tensor.
+        bool has_tset = false;
+        uint32_t tset_id = 0;
+        uint32_t tset_n = 0;
         const uint8_t* ipc = nullptr;
         size_t ipc_len = 0;
         std::vector<std::pair<std::string_view, uint64_t>> blocks;
@@ -215,6 +221,8 @@ class Server {
     void reply_local(Conn* c, const ReqCtx& ctx, int code);
     void reply_query(Conn* c, const ReqCtx& ctx, int value);
     void op_shm_setup(Conn* c, const std::vector<uint8_t>& body);
+    void op_tset_register(Conn* c, const std::vector<uint8_t>& body);
+    void op_tset_release(Conn* c, const std::vector<uint8_t>& body);
     void shm_teardown(Conn* c);       // owner loop thread; joins the poller
     void shm_poll_main(ShmPeer* p);   // poller thread body
     std::atomic<int> shm_peers_{0};
@@ -336,6 +344,24 @@ struct Server::Conn : RefCounted {
     // remain/fabric_inflight keep this >0; the cache flush in
     // resolve_client_base only runs when the flusher is the sole pinner.
     std::atomic<int> ipc_pin{0};
+
+    // Registered tensor sets (OP_TSET_REGISTER), by id; guarded by ipc_mu and
+    // released with the connection. A request copies the shared_ptr, so a set
+    // released while its job is in flight stays whole until the job is done.
+    struct TensorSet {
+        int32_t device = 0;
+        // Resolved address of every tensor's first byte, in set order; shared
+        // with the copy jobs and immutable.
+        std::shared_ptr<const std::vector<uint64_t>> bases;
+        uint64_t min_extent = 0;  // the smallest tensor: what every part must fit
+        bool bases16 = false;     // every base a multiple of 16
+        std::vector<void*> mappings;  // distinct IPC mappings the set holds
+    };
+    std::map<uint32_t, std::shared_ptr<const TensorSet>> tsets;
+    uint32_t next_tset_id = 1;
+    // IPC mapping base -> live sets that use it. The cache flush never closes
+    // such a mapping.
+    std::map<void*, int> ipc_set_refs;
 
     // fabric: blocks allocated for this conn, not yet committed.
     std::unordered_map<uint64_t, Ref<BlockEntry>> pending_rdma;

@@ -221,10 +221,22 @@ bool Shard::submit_copy(CopyJob&& job) {
         return true;
     }
     const bool transforms = page_codec_transforms(job.codec);
-    if (!segments_legal(job.codec, job.bytes_per_block, job.n_segments, job.segment_stride))
+    // A tensor set replaces the segment rule by its own, which contains it.
+    const bool tset = job.tensor_bases != nullptr;
+    const size_t n_tensors = tset ? job.tensor_bases->size() : 0;
+    if (tset) {
+        if (!tensors_legal(job.codec, job.bytes_per_block, job.n_segments, job.segment_stride,
+                           n_tensors) ||
+            job.segs_per_tensor * n_tensors != job.n_segments || slice_is_set(job.slice))
+            return false;
+    } else if (!segments_legal(job.codec, job.bytes_per_block, job.n_segments,
+                               job.segment_stride)) {
         return false;
+    }
     const bool segmented = job.n_segments > 1;
-    const PageSegments seg{job.n_segments, segmented ? job.segment_stride : 0};
+    // The stride is applied between the segments of ONE tensor only.
+    const bool strided = tset ? job.segs_per_tensor > 1 : segmented;
+    const PageSegments seg{job.n_segments, strided ? job.segment_stride : 0};
     // A slice is a read-side geometry, and the job's page is the sliced page.
     const bool sliced = slice_is_set(job.slice);
     if (sliced && (job.dir != PageDir::kLoad || !slice_legal(job.codec, job.slice, seg) ||
@@ -252,6 +264,8 @@ bool Shard::submit_copy(CopyJob&& job) {
             sub.n_segments = job.n_segments;
             sub.segment_stride = job.segment_stride;
             sub.slice = job.slice;
+            sub.tensor_bases = job.tensor_bases;
+            sub.segs_per_tensor = job.segs_per_tensor;
             sub.scales = job.scales;
             sub.scales_off = job.scales_off + off;
             sub.src.assign(job.src.begin() + static_cast<long>(off),
@@ -288,6 +302,25 @@ bool Shard::submit_copy(CopyJob&& job) {
             if (job.done) job.done(true);
             return true;
         }
+        if (tset) {
+            // Segment s of a page lies in tensor s / per_tensor, at the
+            // block's offset plus (s % per_tensor) strides; the pool side is
+            // the concatenation.
+            const size_t seg_bytes = job.bytes_per_block / seg.n;
+            const bool store = job.dir == PageDir::kStore;
+            const std::vector<uint64_t>& base = *job.tensor_bases;
+            for (size_t i = 0; i < n; i++)
+                for (uint32_t sg = 0; sg < seg.n; sg++) {
+                    const uint64_t client = base[sg / job.segs_per_tensor] +
+                                            (store ? job.src[i] : job.dst[i]) +
+                                            (sg % job.segs_per_tensor) * seg.stride_bytes;
+                    const uint64_t pool = (store ? job.dst[i] : job.src[i]) + sg * seg_bytes;
+                    memcpy(reinterpret_cast<void*>(store ? pool : client),
+                           reinterpret_cast<const void*>(store ? client : pool), seg_bytes);
+                }
+            if (job.done) job.done(true);
+            return true;
+        }
         const size_t seg_bytes = job.bytes_per_block / seg.n;
         const uint64_t src_step = job.dir == PageDir::kStore ? seg.stride_bytes : seg_bytes;
         const uint64_t dst_step = job.dir == PageDir::kStore ? seg_bytes : seg.stride_bytes;
@@ -305,6 +338,10 @@ bool Shard::submit_copy(CopyJob&& job) {
     // size: both must keep the 16-byte alignment too.
     if (segmented)
         aligned = aligned && (job.bytes_per_block / seg.n) % 16 == 0 && seg.stride_bytes % 16 == 0;
+    // The client descriptors below are offsets inside every tensor: the
+    // bases must keep the alignment as well.
+    if (tset)
+        for (uint64_t base : *job.tensor_bases) aligned = aligned && base % 16 == 0;
     // A slice's pieces start at offset + p * stride on the pool side and at
     // multiples of the piece on the client side.
     if (sliced)
@@ -350,8 +387,9 @@ bool Shard::submit_copy(CopyJob&& job) {
     StreamCtx& sc = streams_[pick];
 
     // Small aligned batches: descriptors ride in the kernel arguments.
-    // (Segmented and sliced jobs always use the pinned-descriptor kernels.)
-    if (aligned && n <= 16 && !transforms && !segmented && !sliced) {
+    // (Segmented, sliced and tensor-set jobs always use the pinned-descriptor
+    // kernels.)
+    if (aligned && n <= 16 && !transforms && !segmented && !sliced && !tset) {
         Slot* slot = acquire_slot(sc);
         if (!slot) return false;
         bool ok = gpu::set_device(opt_.device) &&
@@ -397,6 +435,24 @@ bool Shard::submit_copy(CopyJob&& job) {
             ok = ok && gpu::launch_load_sliced(opt_.device, sc.stream, job.codec, dsrc, ddst,
                                                slot->h_scale, static_cast<int>(take), job.slice,
                                                seg, aligned);
+        } else if (tset) {
+            // The table of bases goes into each launch's kernel arguments.
+            const gpu::TensorTable table{job.tensor_bases->data(),
+                                         static_cast<uint32_t>(n_tensors)};
+            if (!transforms) {
+                ok = ok && gpu::launch_copy_blocks_tset(opt_.device, sc.stream, dsrc, ddst,
+                                                        static_cast<int>(take),
+                                                        job.bytes_per_block, aligned, seg,
+                                                        job.dir, table);
+            } else {
+                if (page_scale && job.dir == PageDir::kLoad)
+                    memcpy(slot->h_scale, job.scales->data() + job.scales_off + off,
+                           take * sizeof(float));
+                ok = ok && gpu::launch_transform_blocks_tset(
+                               opt_.device, sc.stream, job.codec, job.dir, dsrc, ddst,
+                               slot->h_scale, static_cast<int>(take),
+                               job.bytes_per_block / kPageElemBytes, aligned, seg, table);
+            }
         } else if (!transforms) {
             ok = ok && gpu::launch_copy_blocks(opt_.device, sc.stream, dsrc, ddst,
                                                static_cast<int>(take), job.bytes_per_block,

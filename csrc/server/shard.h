@@ -63,6 +63,16 @@ class Shard {
         // kLoad only; segments apply to the sliced page. Such a job never
         // takes the inline-argument path.
         PageSlice slice;
+        // Tensor sets (core/page_codec.h, tensors_legal): with tensor_bases
+        // set, every page's client side spans tensor_bases->size() tensors.
+        // The CLIENT side's descriptors (src for kStore, dst for kLoad) are
+        // then byte OFFSETS, the same inside every tensor; n_segments is the
+        // total over all tensors and segs_per_tensor their count in one
+        // (n_segments == tensors * segs_per_tensor). The resolved bases are
+        // shared and immutable: fan-out sub-jobs hold the same vector. Such a
+        // job never takes the inline-argument path and carries no slice.
+        std::shared_ptr<const std::vector<uint64_t>> tensor_bases;
+        uint32_t segs_per_tensor = 0;
         // Codecs with a per-page scale: block i's scale is
         // (*scales)[scales_off + i], written before done() by kStore and
         // read at submit by kLoad. Fan-out sub-jobs share the vector.

@@ -8,6 +8,7 @@ extensions (fingerprint_blocks, get_server_stats, unregister_server).
 from .lib import (
     InfinityConnection,
     PageSlice,
+    TensorSet,
     DisableTorchCaching,
     ClientConfig,
     ServerConfig,
@@ -32,6 +33,7 @@ from .lib import (
 __all__ = [
     "InfinityConnection",
     "PageSlice",
+    "TensorSet",
     "DisableTorchCaching",
     "register_server",
     "unregister_server",

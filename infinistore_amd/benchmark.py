@@ -54,6 +54,12 @@ def parse_args():
                    help="segmented pages (local-GPU path): lay each client "
                         "tensor out [N, n_pages, page/N] and move every page "
                         "as N segments a plane apart; 1 = contiguous pages")
+    p.add_argument("--fused-layers", action="store_true",
+                   help="with --shape and --local-gpu: one separately allocated "
+                        "tensor per layer, registered as a tensor set; every "
+                        "block travels as ONE page under ONE key spanning all "
+                        "layers (docs/design.md, \"tensor sets\") instead of one "
+                        "key per (layer, block)")
     p.add_argument("--slice", default=None, metavar="H0:H1/H",
                    help="sliced reads (local-GPU path): view every page as "
                         "[--slice-rows, H, head] and read only heads H0..H1 of "
@@ -146,7 +152,87 @@ def make_buffers(args, conn, local, device):
     return srcs, dsts, blocks_per_sub
 
 
+# Requests and keys sent by the timed loops, over all iterations of a process.
+COUNTS = {"requests": 0, "keys": 0, "seconds": 0.0}
+
+
+def _count(n_keys):
+    COUNTS["requests"] += 1
+    COUNTS["keys"] += n_keys
+
+
+def make_fused_buffers(args, conn, device):
+    """--fused-layers: one src and one dst tensor per layer, each its own
+    allocation of pages_per_layer pages, registered as two tensor sets.
+    Returns (srcs, dsts, src_set, dst_set)."""
+    n_layers = SHAPES[args.shape][0]
+    block_bytes = args.block_size << 10
+    dt = torch.bfloat16 if args.quant else torch.float32
+    es = 2 if args.quant else 4
+    pages = (args.size << 20) // block_bytes // n_layers
+    elems = pages * block_bytes // es
+    srcs = [torch.rand(elems, dtype=dt, device=device) for _ in range(n_layers)]
+    dsts = [torch.zeros(elems, dtype=dt, device=f"cuda:{args.dst_gpu}") for _ in range(n_layers)]
+    torch.cuda.synchronize()
+    return srcs, dsts, conn.register_tensor_set(srcs), conn.register_tensor_set(dsts)
+
+
+def run_once_fused(args, conn, device, bufs=None):
+    """One iteration of --fused-layers: block b of ALL layers is one page of
+    n_layers * page_elems elements under one key. Requests carry ~64 MB, as
+    the per-layer read chunks do; writes are async until the final sync and
+    reads ticketed, as in run_once."""
+    import numpy as np
+
+    n_layers = SHAPES[args.shape][0]
+    block_bytes = args.block_size << 10
+    es = 2 if args.quant else 4
+    page_elems = block_bytes // es
+    srcs, dsts, src_set, dst_set = (bufs if bufs is not None
+                                    else make_fused_buffers(args, conn, device))
+    pages = srcs[0].numel() // page_elems
+    fused_elems = n_layers * page_elems
+    total_bytes = pages * fused_elems * es
+    run = uuid.uuid4().hex
+    keys = [f"{run}-{i}" for i in range(pages)]
+    offs = np.arange(pages, dtype=np.uint64) * np.uint64(page_elems)
+    chunk = max(1, (64 << 20) // (fused_elems * es))
+
+    t0 = time.perf_counter()
+    for c0 in range(0, pages, chunk):
+        c1 = min(c0 + chunk, pages)
+        conn.write_pages(None, keys[c0:c1], offs[c0:c1], fused_elems, quant=args.quant,
+                         tensor_set=src_set)
+        _count(c1 - c0)
+    conn.sync()
+    w_time = time.perf_counter() - t0
+
+    t0 = time.perf_counter()
+    tickets = []
+    for c0 in range(0, pages, chunk):
+        c1 = min(c0 + chunk, pages)
+        tickets.append(conn.read_pages_async(None, keys[c0:c1], offs[c0:c1], fused_elems,
+                                             tensor_set=dst_set))
+        _count(c1 - c0)
+    for tk in tickets:
+        conn.wait_read(tk)
+    conn.sync()
+    r_time = time.perf_counter() - t0
+    COUNTS["seconds"] += w_time + r_time
+
+    if args.verify:
+        for a, b in zip(srcs, dsts):
+            assert _close(a.cpu(), b.cpu(), args.quant), "verification failed (fused)"
+    try:
+        conn.delete_keys(keys)
+    except Exception:
+        pass
+    return total_bytes / w_time / 1e6, total_bytes / r_time / 1e6
+
+
 def run_once(args, conn, local, device, bufs=None):
+    if getattr(args, "fused_layers", False):
+        return run_once_fused(args, conn, device, bufs)
     block_bytes = args.block_size << 10
     total_bytes = args.size << 20
     n_blocks = total_bytes // block_bytes
@@ -203,6 +289,7 @@ def run_once(args, conn, local, device, bufs=None):
             blocks = conn.allocate_rdma([p[0] for p in pairs], block_bytes)
             conn.rdma_write_cache(srcs[t_idx], [p[1] for p in pairs],
                                   page_elems, blocks)
+        _count(len(pairs))
     conn.sync()
     w_time = time.perf_counter() - t0
 
@@ -224,6 +311,7 @@ def run_once(args, conn, local, device, bufs=None):
                 ks = [keys[i] for i in range(c0, c1)]
                 offs = np.asarray([sub_of(i)[1] for i in range(c0, c1)],
                                   dtype=np.uint64)
+                _count(c1 - c0)
                 if sg and not args.slice_baseline:
                     offs = offs // np.uint64(page_elems) * np.uint64(sliced_elems)
                     tickets.append(conn.read_pages_async(outs[t_idx], ks, offs,
@@ -250,8 +338,10 @@ def run_once(args, conn, local, device, bufs=None):
             conn.read_cache(dsts[t_idx],
                             [(keys[i], sub_of(i)[1]) for i in range(lo, hi)],
                             page_elems)
+            _count(hi - lo)
     conn.sync()
     r_time = time.perf_counter() - t0
+    COUNTS["seconds"] += w_time + r_time
 
     if args.verify and sg:
         for a, o in zip(srcs, outs):
@@ -357,7 +447,8 @@ def _worker(args_dict, q, barrier, wid):
     conn = None
     try:
         conn = make_conn(ns, local)
-        bufs = make_buffers(ns, conn, local, device)
+        bufs = (make_fused_buffers(ns, conn, device) if getattr(ns, "fused_layers", False)
+                else make_buffers(ns, conn, local, device))
         run_once(ns, conn, local, device, bufs)  # warm: IPC opens, allocator
         barrier.wait(timeout=600)  # start all clients together (steady state)
         t0 = time.perf_counter()
@@ -426,6 +517,12 @@ def main():
             raise SystemExit("--segments needs --local-gpu")
         if args.segments < 1 or ((args.block_size << 10) // es) % args.segments:
             raise SystemExit("--segments must divide the page's element count")
+    if args.fused_layers:
+        if not args.shape or not args.local_gpu:
+            raise SystemExit("--fused-layers needs --shape and --local-gpu")
+        if args.segments != 1 or args.slice:
+            raise SystemExit("--fused-layers moves whole contiguous per-layer parts: "
+                             "no --segments, no --slice")
     if args.slice:
         if not args.local_gpu or args.segments != 1:
             raise SystemExit("--slice needs --local-gpu and --segments 1")
@@ -492,14 +589,23 @@ def main():
     conn = make_conn(args, local)
     try:
         writes, reads = [], []
+        # one set of tensors (and one registration) for all iterations, as an
+        # engine holds its layer tensors
+        bufs = make_fused_buffers(args, conn, device) if args.fused_layers else None
         for it in range(args.iteration):
-            w, r = run_once(args, conn, local, device)
+            w, r = run_once(args, conn, local, device, bufs)
             writes.append(w)
             reads.append(r)
             print(f"[iter {it}] write cache: {w:.2f} MB/s, read cache: {r:.2f} MB/s")
+        rps = COUNTS["requests"] / COUNTS["seconds"] if COUNTS["seconds"] else 0.0
+        print(f"requests: {COUNTS['requests']} carrying {COUNTS['keys']} keys in "
+              f"{COUNTS['seconds']:.3f} s of timed windows: {rps:.0f} requests/s")
         summary = {
             "write_MBps": round(statistics.mean(writes), 2),
             "read_MBps": round(statistics.mean(reads), 2),
+            "requests": COUNTS["requests"],
+            "keys": COUNTS["keys"],
+            "requests_per_s": round(rps, 1),
             "block_kb": args.block_size,
             "size_mb": args.size,
             "path": "local_gpu" if local else "fabric",

@@ -16,6 +16,7 @@ it (duck-typed; vLLM not required).
 import hashlib
 from typing import List, Optional, Sequence
 
+import numpy as np
 import torch
 
 from . import lib
@@ -68,6 +69,7 @@ class PagedKVConnector:
         self.conn.connect()
         self.local = local
         self._registered = set()
+        self._tensor_sets = {}  # (ptr, numel) per layer -> registered TensorSet
 
     def close(self):
         self.conn.close()
@@ -165,6 +167,78 @@ class PagedKVConnector:
                                               page_slice=page_slice)
         except Exception:
             return None
+
+    # -- all layers under one key (tensor sets) --------------------------------
+    # Engines allocate one KV tensor per layer. Registered once as a tensor
+    # set (docs/design.md, "tensor sets"), block b of ALL layers travels as one
+    # page of n_layers * page_elems elements under ONE key: one request per
+    # save and one per load instead of n_layers of each. Local path only. The
+    # key scheme drops the layer index, so fused and per-layer keys of one
+    # page hash never collide. With quant="fp8" the page's single scale spans
+    # all layers.
+    def save_all_layers(self, kvs, page_keys: List[str], page_offsets, page_elems: int,
+                        segments: int = 1, segment_stride: int = 0):
+        """Store block `page_offsets[i]` (elements, the same in every layer
+        tensor) of all `kvs` under page_keys[i]. page_elems, segments and
+        segment_stride describe ONE layer's part, as in save_layer."""
+        ts = self._tensor_set(kvs)
+        self.conn.write_pages(None, [self._fused_key(k) for k in page_keys], page_offsets,
+                              page_elems * len(kvs), quant=self.quant,
+                              segments=segments * len(kvs), segment_stride=segment_stride,
+                              tensor_set=ts)
+
+    def load_all_layers(self, kvs_out, page_keys: List[str], page_offsets, page_elems: int,
+                        segments: int = 1, segment_stride: int = 0) -> bool:
+        """Gather the pages into all layer tensors with one request. False if
+        any page is missing; a refused geometry raises ValueError."""
+        tk = self.load_all_layers_async(kvs_out, page_keys, page_offsets, page_elems,
+                                        segments, segment_stride)
+        return tk is not None and self.wait_load(tk)
+
+    def load_all_layers_async(self, kvs_out, page_keys: List[str], page_offsets,
+                              page_elems: int, segments: int = 1, segment_stride: int = 0):
+        """Ticketed form of load_all_layers: one ticket for all layers (None
+        if the request failed at once); wait_load(ticket) before use."""
+        ts = self._tensor_set(kvs_out)
+        offs = np.asarray(page_offsets, dtype=np.uint64)
+        total = segments * len(kvs_out)
+        self.conn._check_tensor_set(ts, offs, page_elems * len(kvs_out), total, segment_stride)
+        try:
+            return self.conn.read_pages_async(None, [self._fused_key(k) for k in page_keys],
+                                              offs, page_elems * len(kvs_out), segments=total,
+                                              segment_stride=segment_stride, tensor_set=ts)
+        except Exception:
+            return None
+
+    def cached_pages_fused(self, page_keys: List[str]) -> int:
+        """cached_pages for pages saved with save_all_layers."""
+        try:
+            return self.conn.get_match_last_index([self._fused_key(k) for k in page_keys]) + 1
+        except Exception:
+            return 0
+
+    def evict_fused(self, page_keys: List[str]) -> int:
+        return self.conn.delete_keys([self._fused_key(k) for k in page_keys])
+
+    def _tensor_set(self, kvs):
+        """The registered set of these layer tensors, registered on first use.
+        A connection holds few sets: the oldest is released for a new one."""
+        if not self.local:
+            raise ValueError("all-layer pages use tensor sets, which need the local GPU path")
+        if len(kvs) != self.n_layers:
+            raise ValueError(f"{len(kvs)} layer tensors for {self.n_layers} layers")
+        ident = tuple((t.data_ptr(), t.numel()) for t in kvs)
+        ts = self._tensor_sets.get(ident)
+        if ts is None:
+            if len(self._tensor_sets) >= self.conn.MAX_TENSOR_SETS:
+                self.conn.sync()  # nothing of the set to be released is in flight
+                self.conn.release_tensor_set(self._tensor_sets.pop(next(iter(self._tensor_sets))))
+            ts = self.conn.register_tensor_set([t.view(-1) for t in kvs])
+            self._tensor_sets[ident] = ts
+        return ts
+
+    def _fused_key(self, page_hash: str) -> str:
+        return f"{self.model_tag}/ALL/{page_hash}"
 
     def wait_load(self, ticket) -> bool:
         try:

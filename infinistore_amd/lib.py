@@ -274,6 +274,19 @@ class PageSlice(NamedTuple):
     count: int = 1
 
 
+class TensorSet:
+    """A registered tensor set (InfinityConnection.register_tensor_set): the
+    server-side id and the tensors, which it keeps alive."""
+
+    def __init__(self, conn, set_id: int, tensors):
+        self.conn = conn
+        self.set_id = set_id
+        self.tensors = list(tensors)
+
+    def __len__(self):
+        return len(self.tensors)
+
+
 class InfinityConnection:
     """Connection to an infinistore-amd server (local IPC path or
     RDMA-semantics path over the negotiated fabric)."""
@@ -461,9 +474,103 @@ class InfinityConnection:
         sl = PageSlice(*page_slice)
         return (sl.count, sl.page_size, sl.offset, sl.piece, sl.stride)
 
-    def write_pages(self, cache: torch.Tensor, keys, offsets, page_size: int,
+    # Tensor sets (csrc/core/page_codec.h, docs/design.md): the most tensors
+    # one set may have and the most sets one connection may hold.
+    MAX_PAGE_TENSORS = 128
+    MAX_TENSOR_SETS = 16
+
+    def register_tensor_set(self, tensors) -> "TensorSet":
+        """Register an ordered list of tensors (one device, one dtype, e.g. an
+        engine's per-layer KV tensors) on this connection, once. The returned
+        TensorSet stands in for `cache` in write_pages / read_pages /
+        read_pages_async (``tensor_set=``): a page is then the concatenation,
+        in set order, of one equal part from each tensor, every part at the
+        SAME offset inside its own tensor, so one key and one request move a
+        block of all layers. The set keeps the tensors alive. Local path
+        only."""
+        tensors = list(tensors)
+        if not self.local_connected:
+            raise ValueError("tensor sets use the local GPU path")
+        if not 1 <= len(tensors) <= self.MAX_PAGE_TENSORS:
+            raise ValueError(f"a tensor set has 1..{self.MAX_PAGE_TENSORS} tensors")
+        for t in tensors:
+            if t.device != tensors[0].device or t.dtype != tensors[0].dtype:
+                raise ValueError("the tensors of a set share one device and one dtype")
+            if not t.is_contiguous():
+                raise ValueError("the tensors of a set must be contiguous")
+        for t in tensors:
+            self._verify(t)
+        es = tensors[0].element_size()
+        set_id = self.conn.register_tensor_set(
+            [t.data_ptr() for t in tensors], [t.numel() * es for t in tensors],
+            _remap_device_id(tensors[0]))
+        if set_id <= 0:
+            raise Exception(f"Failed to register the tensor set, ret = {set_id}")
+        return TensorSet(self, set_id, tensors)
+
+    def release_tensor_set(self, ts: "TensorSet") -> None:
+        """Release a registered set: its id is unknown to the server from then
+        on, and the TensorSet can no longer be used."""
+        if ts.conn is not self or ts.set_id is None:
+            raise ValueError("not a live tensor set of this connection")
+        ret = self.conn.release_tensor_set(ts.set_id)
+        ts.set_id = None
+        ts.tensors = []
+        if ret < 0:
+            raise Exception(f"Failed to release the tensor set, ret = {ret}")
+
+    def _check_tensor_set(self, ts, offsets, page_size: int, segments: int,
+                          segment_stride: int, quant: Optional[str] = None) -> None:
+        """Refuse (ValueError) a request over a tensor set the store cannot
+        serve, before anything is sent: tensors_legal's rules in elements and
+        the bound check that keeps every part inside every tensor."""
+        if not self.local_connected:
+            raise ValueError("tensor sets use the local GPU path")
+        if not isinstance(ts, TensorSet) or ts.conn is not self or ts.set_id is None:
+            raise ValueError("not a live tensor set of this connection")
+        G = len(ts.tensors)
+        if not 1 <= segments <= self.MAX_PAGE_SEGMENTS or segments % G != 0:
+            raise ValueError("segments is the total over all tensors: a multiple of their "
+                             f"number, at most {self.MAX_PAGE_SEGMENTS}")
+        if page_size <= 0 or page_size % segments != 0:
+            raise ValueError("page_size must be a positive multiple of segments")
+        seg, per = page_size // segments, segments // G
+        if per > 1 and segment_stride < seg:
+            raise ValueError("segment_stride is smaller than a segment: the segments "
+                             "of a page would overlap")
+        es = ts.tensors[0].element_size()
+        if quant is not None:
+            multiple = self.QUANT_MODES[quant][1]
+            if ts.tensors[0].dtype != torch.bfloat16:
+                raise ValueError(f"{quant} quant requires bf16 tensors")
+            if seg % multiple != 0:
+                raise ValueError(f"{quant} quant needs segments of a multiple of "
+                                 f"{multiple} elements")
+            if per > 1 and (segment_stride * es) % 16 != 0:
+                raise ValueError(f"{quant} quant needs a segment_stride that is a "
+                                 "multiple of 16 bytes")
+            if any(t.data_ptr() % 16 for t in ts.tensors) or (offsets % np.uint64(8)).any():
+                raise ValueError(f"{quant} quant needs 16-byte-aligned tensors and page "
+                                 "offsets that are multiples of 8 elements")
+        span = (per - 1) * segment_stride + seg if per > 1 else seg
+        if len(offsets) and int(max(offsets)) + span > min(t.numel() for t in ts.tensors):
+            raise ValueError("a page part extends outside a tensor of the set")
+
+    def _rw_tensor_set(self, op, ts, keys, offs, page_size, sync, flags, segments,
+                       segment_stride, ticketed=False):
+        if not isinstance(keys, (bytes, bytearray, memoryview)):
+            keys = self.pack_keys(keys)
+        es = ts.tensors[0].element_size()
+        per = segments // len(ts.tensors)
+        return self.conn.rw_tset_blob(
+            op, keys, offs, es, page_size * es, ts.set_id, len(ts.tensors),
+            _remap_device_id(ts.tensors[0]), sync, flags, segments,
+            segment_stride if per > 1 else 0, ticketed)
+
+    def write_pages(self, cache: Optional[torch.Tensor], keys, offsets, page_size: int,
                     sync: bool = False, quant: Optional[str] = None,
-                    segments: int = 1, segment_stride: int = 0, **unsupported):
+                    segments: Optional[int] = None, segment_stride: int = 0,
+                    tensor_set=None, **unsupported):
         """sync=True completes the write in ONE round trip (the response is
         sent when the copy finishes); sync=False (default) returns after the
         server accepts, so uploads overlap compute — call sync() later.
@@ -498,6 +605,13 @@ class InfinityConnection:
         only; an illegal geometry or a page that leaves the tensor is a
         ValueError before anything is sent.
 
+        tensor_set=ts (from register_tensor_set) in place of `cache` (pass
+        None): each page spans all tensors of the set, `offsets` are relative
+        to every tensor, page_size is the whole page across all tensors and
+        `segments` the total (default: one per tensor; a multiple of the number of tensors; with one
+        segment per tensor segment_stride is ignored). fp8 then keeps one
+        scale over the parts of all tensors.
+
         Slices are read-only: write_pages has no page_slice parameter, and
         passing one is a ValueError."""
         if "page_slice" in unsupported:
@@ -505,6 +619,22 @@ class InfinityConnection:
         if unsupported:
             raise TypeError(f"write_pages() got an unexpected keyword argument "
                             f"{next(iter(unsupported))!r}")
+        if tensor_set is not None:
+            if cache is not None:
+                raise ValueError("pass either cache or tensor_set")
+            if quant is not None and quant not in self.QUANT_MODES:
+                raise ValueError(f"unsupported quant mode {quant!r}")
+            if segments is None:  # not given: one segment per tensor
+                segments = len(getattr(tensor_set, "tensors", ())) or 1
+            offs = np.asarray(offsets, dtype=np.uint64)
+            self._check_tensor_set(tensor_set, offs, page_size, segments, segment_stride, quant)
+            flags = self.QUANT_MODES[quant][0] if quant is not None else 0
+            ret, _ = self._rw_tensor_set(self.OP_W, tensor_set, keys, offs, page_size, sync,
+                                         flags, segments, segment_stride)
+            if ret < 0:
+                raise Exception(f"Failed to write to infinistore, ret = {ret}")
+            return 0
+        segments = 1 if segments is None else segments
         self._verify(cache)
         if segments != 1 and not self.local_connected:
             raise ValueError("segmented pages use the local GPU path")
@@ -544,9 +674,9 @@ class InfinityConnection:
             raise Exception(f"Failed to write to infinistore, ret = {ret}")
         return 0
 
-    def read_pages(self, cache: torch.Tensor, keys, offsets, page_size: int,
-                   segments: int = 1, segment_stride: int = 0,
-                   page_slice: Optional[PageSlice] = None):
+    def read_pages(self, cache: Optional[torch.Tensor], keys, offsets, page_size: int,
+                   segments: Optional[int] = None, segment_stride: int = 0,
+                   page_slice: Optional[PageSlice] = None, tensor_set=None):
         """segments / segment_stride: scatter each page into that many equal
         pieces of `cache` (see write_pages), however the page was written.
         Local path only.
@@ -560,7 +690,21 @@ class InfinityConnection:
         and stride are multiples of 8 and 32 elements (the server answers
         INVALID_REQ otherwise). Only the requested elements are read and
         dequantized. Local path only; an illegal geometry or a page that
-        leaves the tensor is a ValueError before anything is sent."""
+        leaves the tensor is a ValueError before anything is sent.
+
+        tensor_set=ts in place of `cache` (pass None): scatter each page over
+        the tensors of the set (see write_pages), however it was written.
+        Not together with page_slice."""
+        if tensor_set is not None:
+            offs = self._tensor_set_read_args(cache, tensor_set, offsets, page_size,
+                                              segments, segment_stride, page_slice)
+            segments = len(tensor_set.tensors) if segments is None else segments
+            ret, _ = self._rw_tensor_set(self.OP_R, tensor_set, keys, offs, page_size, False,
+                                         0, segments, segment_stride)
+            if ret < 0:
+                raise Exception(f"Failed to read from infinistore, ret = {ret}")
+            return
+        segments = 1 if segments is None else segments
         self._verify(cache)
         if segments != 1 and not self.local_connected:
             raise ValueError("segmented pages use the local GPU path")
@@ -594,15 +738,37 @@ class InfinityConnection:
         if ret < 0:
             raise Exception(f"Failed to read from infinistore, ret = {ret}")
 
-    def read_pages_async(self, cache: torch.Tensor, keys, offsets, page_size: int,
-                         segments: int = 1, segment_stride: int = 0,
-                         page_slice: Optional[PageSlice] = None):
+    def _tensor_set_read_args(self, cache, tensor_set, offsets, page_size, segments,
+                              segment_stride, page_slice):
+        if cache is not None:
+            raise ValueError("pass either cache or tensor_set")
+        if page_slice is not None:
+            raise ValueError("page_slice and tensor_set cannot be combined")
+        if segments is None:  # not given: one segment per tensor
+            segments = len(getattr(tensor_set, "tensors", ())) or 1
+        offs = np.asarray(offsets, dtype=np.uint64)
+        self._check_tensor_set(tensor_set, offs, page_size, segments, segment_stride)
+        return offs
+
+    def read_pages_async(self, cache: Optional[torch.Tensor], keys, offsets, page_size: int,
+                         segments: Optional[int] = None, segment_stride: int = 0,
+                         page_slice: Optional[PageSlice] = None, tensor_set=None):
         """Ticketed read (local path, shm ring): pushes the request and
         returns a ticket; call wait_read(ticket) before using the data. Lets
         an engine overlap its own work (or further requests) with the copy —
         e.g. prefetching the next sequence's KV pages while decoding. Falls
         back to a blocking read (ticket 0) when the ring is unavailable.
-        segments / segment_stride / page_slice as in read_pages."""
+        segments / segment_stride / page_slice / tensor_set as in read_pages."""
+        if tensor_set is not None:
+            offs = self._tensor_set_read_args(cache, tensor_set, offsets, page_size,
+                                              segments, segment_stride, page_slice)
+            segments = len(tensor_set.tensors) if segments is None else segments
+            ret, ticket = self._rw_tensor_set(self.OP_R, tensor_set, keys, offs, page_size,
+                                              True, 0, segments, segment_stride, ticketed=True)
+            if ret < 0:
+                raise Exception(f"Failed to read from infinistore, ret = {ret}")
+            return ticket
+        segments = 1 if segments is None else segments
         self._verify(cache)
         if segments != 1 and not self.local_connected:
             raise ValueError("segmented pages use the local GPU path")

@@ -81,16 +81,42 @@ class InfiniStoreKVAdapter:
             fetches only those heads. Works in both layouts and needs the
             local path. Such an adapter is load-only: save_kv_layer raises
             ValueError. Keys and prefix lookups are the prefill engine's.
+        layer_pages: "per_layer" (default): one key per (layer, block), one
+            request per layer. "fused": one key per block for ALL layers
+            (docs/design.md, "tensor sets"): the engine's per-layer tensors
+            are registered once as a tensor set, save_kv_layer only records
+            its arguments, wait_for_save issues ONE write, start_load_kv ONE
+            read, and wait_for_layer_load waits on that one ticket. Works
+            with both kv_layout values; needs the local path and layer
+            tensors of one size; with head_range it raises ValueError
+            (slices over a tensor set are not supported). The key scheme
+            drops the layer index, so fused and per-layer pages of one model
+            tag never collide, and neither kind of adapter sees the other's
+            pages. With quant="fp8" the page's one scale spans all layers.
     """
 
     KV_LAYOUTS = ("block_major", "kv_major")
+    LAYER_PAGES = ("per_layer", "fused")
 
     def __init__(self, host: str, port: int, model_tag: str, n_layers: int,
                  block_tokens: int, page_elems: int, local: bool = True,
                  quant: Optional[str] = None, kv_layout: str = "block_major",
                  stored_kv_heads: Optional[int] = None,
                  head_range: Optional[Sequence[int]] = None,
-                 head_dim: Optional[int] = None):
+                 head_dim: Optional[int] = None, layer_pages: str = "per_layer"):
+        if layer_pages not in self.LAYER_PAGES:
+            raise ValueError(f"layer_pages must be one of {self.LAYER_PAGES}")
+        if layer_pages == "fused":
+            if head_range is not None:
+                raise ValueError('layer_pages="fused" cannot be combined with head_range: '
+                                 "a tensor set takes no slice")
+            if not local:
+                raise ValueError('layer_pages="fused" uses tensor sets, which need the '
+                                 "local GPU path")
+        self.fused = layer_pages == "fused"
+        self._recorded: Dict[int, tuple] = {}  # fused: layer -> save_kv_layer arguments
+        self._fused_ticket = None
+        self._fused_result: Optional[bool] = None
         self._page_slice = None
         if head_range is not None:
             if stored_kv_heads is None or head_dim is None:
@@ -140,7 +166,8 @@ class InfiniStoreKVAdapter:
         keys = self._page_keys(token_ids)
         if not keys:
             return 0
-        hit_pages = self._conn.cached_pages(keys)
+        hit_pages = (self._conn.cached_pages_fused(keys) if self.fused
+                     else self._conn.cached_pages(keys))
         hit_tokens = hit_pages * self.block_tokens
         return max(0, hit_tokens - num_computed_tokens)
 
@@ -164,6 +191,12 @@ class InfiniStoreKVAdapter:
             raise ValueError(f"block_table has {len(block_table)} entries for "
                              f"{n_pages} full pages")
         s = skip_leading_pages
+        if self.fused:
+            # One write for all layers at wait_for_save: record only.
+            if not 0 <= layer < self.n_layers:
+                raise ValueError(f"layer {layer} of {self.n_layers}")
+            self._recorded[layer] = (kv_cache, tuple(token_ids), tuple(block_table), s)
+            return
         if s >= n_pages:
             return
         offsets = self._offsets(block_table, range(s, n_pages))
@@ -172,7 +205,23 @@ class InfiniStoreKVAdapter:
 
     def wait_for_save(self):
         """Barrier: all save_kv_layer uploads committed (readable by any
-        client, including other hosts)."""
+        client, including other hosts). A fused adapter issues its one
+        write here, from what save_kv_layer recorded for every layer."""
+        if self.fused and self._recorded:
+            rec, self._recorded = self._recorded, {}
+            if sorted(rec) != list(range(self.n_layers)):
+                raise ValueError("a fused save needs save_kv_layer for every layer: got "
+                                 f"{sorted(rec)}")
+            _, token_ids, block_table, skip = rec[0]
+            if any(r[1:] != rec[0][1:] for r in rec.values()):
+                raise ValueError("a fused save needs the same token_ids, block_table and "
+                                 "skip_leading_pages for every layer")
+            keys = self._page_keys(token_ids)
+            if skip < len(keys):
+                kvs = [rec[li][0] for li in range(self.n_layers)]
+                offsets = self._offsets(block_table, range(skip, len(keys)))
+                self._conn.save_all_layers(kvs, keys[skip:], offsets, self.page_elems,
+                                           **self._geometry(kvs[0]))
         self._conn.flush()
 
     # -- worker side: decode load ----------------------------------------------
@@ -196,6 +245,15 @@ class InfiniStoreKVAdapter:
         offsets = self._offsets(block_table, range(len(keys)))
         self._load_tickets.clear()
         self._load_fallback.clear()
+        if self.fused:
+            # One read for all layers; every wait_for_layer_load waits on it.
+            self._fused_result = None
+            self._fused_ticket = self._conn.load_all_layers_async(
+                list(kv_caches), keys, offsets, self.page_elems,
+                **self._geometry(kv_caches[0]))
+            if self._fused_ticket is None:
+                self._fused_result = False
+            return len(keys)
         for li in range(self.n_layers):
             tk = self._conn.load_layer_async(li, kv_caches[li].view(-1), keys,
                                              offsets, self.page_elems,
@@ -209,6 +267,13 @@ class InfiniStoreKVAdapter:
     def wait_for_layer_load(self, layer: int) -> bool:
         """Block until layer ``layer``'s pages have landed. False = a page
         was missing or the read failed (caller recomputes that layer)."""
+        if self.fused:
+            if self._fused_result is None:
+                if self._fused_ticket is None:
+                    return True  # nothing pending (e.g. 0 pages)
+                self._fused_result = self._conn.wait_load(self._fused_ticket)
+                self._fused_ticket = None
+            return self._fused_result
         tk = self._load_tickets.pop(layer, None)
         if tk is not None:
             return self._conn.wait_load(tk)
@@ -222,6 +287,8 @@ class InfiniStoreKVAdapter:
     # -- maintenance -----------------------------------------------------------
     def evict_request(self, token_ids: Sequence[int]) -> int:
         """Drop all layers of this sequence's pages from the store."""
+        if self.fused:
+            return self._conn.evict_fused(self._page_keys(token_ids))
         return self._conn.evict(self._page_keys(token_ids))
 
     # -- internals -------------------------------------------------------------
