@@ -323,7 +323,9 @@ int VerbsClient::read_blocks(const std::vector<std::pair<std::string, uint64_t>>
             int status = static_cast<int>(im.last_imm);
             WARN("verbs read failed: server status %d", status);
             im.last_imm = 0;
-            return status == KEY_NOT_FOUND ? -KEY_NOT_FOUND : -1;
+            // The two statuses a caller can act on keep their code, as on the
+            // TCP fabric (-404 a missing key, -400 a page the entry cannot serve).
+            return status == KEY_NOT_FOUND || status == INVALID_REQ ? -status : -1;
         }
     }
     return 0;

@@ -82,7 +82,22 @@ inline size_t stored_bytes(PageCodec c, size_t page) {
 // Read side: does a block of `stored` bytes hold a logical page of `page`?
 inline bool stored_matches(PageCodec c, size_t stored, size_t page) {
     const PageCodecInfo& i = page_codec_info(c);
-    return stored * i.den == page * i.num;
+    // 128-bit products: a size near 2^64 off the wire must not wrap into a match.
+    using u128 = unsigned __int128;
+    return static_cast<u128>(stored) * i.den == static_cast<u128>(page) * i.num;
+}
+
+// Read side, whole-page request: may a block of `stored` bytes answer a read
+// of `page` bytes? A plain block serves any page up to its own size, and a
+// shorter read returns the block's first `page` bytes (the reference's
+// behaviour, kept); a larger one would run past the block into its neighbour
+// or out of the arena. A compressed block has no usable prefix: the page must
+// be the written one. Sliced and tensor-set reads do not come here: they take
+// stored_matches for every codec. The plain case reads no table row: the read
+// sweep calls this per block under the stripe lock.
+inline bool stored_serves(PageCodec c, size_t stored, size_t page) {
+    if (!page_codec_transforms(c)) return page <= stored;
+    return stored_matches(c, stored, page);
 }
 
 // Segmented pages (docs/design.md, "segmented pages"): on the CLIENT side of

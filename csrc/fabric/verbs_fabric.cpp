@@ -187,10 +187,13 @@ bool Driver::lookup_region(const void* ptr, MrInfo* out) const {
     auto& im = *impl_;
     auto p = reinterpret_cast<uintptr_t>(ptr);
     std::lock_guard<std::mutex> lk(im.mr_mu);
-    for (auto& mr : im.regions) {
-        auto b = reinterpret_cast<uintptr_t>(mr.addr);
-        if (p >= b && p < b + mr.len) {
-            *out = mr;
+    // Newest first: regions are never dropped, so an allocator that hands a
+    // freed tensor's address to a larger one leaves a stale, shorter region in
+    // front of the live one; the last registration of an address is the live one.
+    for (auto it = im.regions.rbegin(); it != im.regions.rend(); ++it) {
+        auto b = reinterpret_cast<uintptr_t>(it->addr);
+        if (p >= b && p < b + it->len) {
+            *out = *it;
             return true;
         }
     }

@@ -1114,6 +1114,19 @@ PYBIND11_MODULE(_native, m) {
 
     // ---- debug/test surface (the codec table: csrc/core/page_codec.h) ----
     m.def("_dbg_page_codec", &page_codec_py, py::arg("flags"), py::arg("page_bytes"));
+    // The read-size predicates, codec by id (0 none, 1 fp8, 2 mxfp4): may a
+    // block of `stored` bytes answer a whole-page read of `page` bytes, and
+    // does it hold exactly that page (sliced and tensor-set reads).
+    m.def("_dbg_stored_serves",
+          [](int codec, size_t stored, size_t page) {
+              return stored_serves(codec_from_id("_dbg_stored_serves", codec), stored, page);
+          },
+          py::arg("codec"), py::arg("stored"), py::arg("page"));
+    m.def("_dbg_stored_matches",
+          [](int codec, size_t stored, size_t page) {
+              return stored_matches(codec_from_id("_dbg_stored_matches", codec), stored, page);
+          },
+          py::arg("codec"), py::arg("stored"), py::arg("page"));
     // The segment-geometry predicate, codec by id (0 none, 1 fp8, 2 mxfp4).
     m.def("_dbg_segments_legal",
           [](int codec, size_t page_bytes, uint64_t n_segments, uint64_t stride_bytes) {

@@ -590,3 +590,154 @@ def test_large_streamed_read(ports):
         conn.close()
     finally:
         ifs.unregister_server()
+
+
+# ---- read sizes (docs/protocol.md, "read sizes") ----------------------------
+# A plain entry serves a whole-page read of at most its own size and returns
+# that prefix; a larger page is INVALID_REQ before anything is copied. The
+# sizes: below the 16 KiB granule, exactly one granule, one granule plus 16.
+READ_SIZE_KEYS = [1000, 16384, 16400]
+SENTINEL = 0xA5
+INVALID_REQ = "ret = -400"
+
+
+@pytest.fixture(scope="module")
+def read_size_server():
+    """One CPU-pool server for all read-size cases (their keys are unique, and
+    a server start and stop costs about 2 s); yields the service port."""
+    from conftest import free_port
+
+    port = free_port()
+    ifs.register_server(ifs.ServerConfig(
+        service_port=port, manage_port=free_port(), prealloc_size=1,
+        minimal_allocate_size=16, cpu_only=True))
+    yield port
+    ifs.unregister_server()
+
+
+def _u8_pattern(n, seed):
+    g = torch.Generator().manual_seed(seed)
+    # never the sentinel, so "untouched" and "copied" cannot be confused
+    t = torch.randint(0, 255, (n,), dtype=torch.uint8, generator=g)
+    t[t == SENTINEL] = 255
+    return t
+
+
+def _put_u8(conn, keys, size, data):
+    conn.register_mr(data)
+    blocks = conn.allocate_rdma(keys, size)
+    conn.rdma_write_cache(data, [i * size for i in range(len(keys))], size, blocks)
+    conn.sync()
+    return blocks
+
+
+def _sentinel_dst(conn, n):
+    dst = torch.full((n,), SENTINEL, dtype=torch.uint8)
+    conn.register_mr(dst)
+    return dst
+
+
+@pytest.mark.parametrize("size", READ_SIZE_KEYS)
+def test_read_size_prefix_and_refusal(read_size_server, size):
+    conn = make_client(read_size_server)
+    try:
+        # the key under test first, then neighbours that an over-read would hit
+        keys = _keys(4)
+        data = _u8_pattern(4 * size, seed=size)
+        _put_u8(conn, keys, size, data)
+        want = data[:size]
+        for page in (size, size - 1, size // 2):
+            dst = _sentinel_dst(conn, 2 * size + 16)
+            conn.read_cache(dst, [(keys[0], 0)], page)
+            conn.sync()
+            assert torch.equal(dst[:page], want[:page]), page
+            assert bool((dst[page:] == SENTINEL).all()), page
+        for page in (size + 1, 2 * size):
+            dst = _sentinel_dst(conn, 2 * size + 16)
+            with pytest.raises(Exception, match=INVALID_REQ):
+                conn.read_cache(dst, [(keys[0], 0)], page)
+            assert bool((dst == SENTINEL).all()), page
+            # the same connection keeps serving
+            conn.read_cache(dst, [(keys[0], 0)], size)
+            conn.sync()
+            assert torch.equal(dst[:size], want)
+            assert bool((dst[size:] == SENTINEL).all())
+    finally:
+        conn.close()
+
+
+@pytest.mark.parametrize("size", READ_SIZE_KEYS)
+def test_read_size_mixed_request_is_refused_whole(read_size_server, size):
+    conn = make_client(read_size_server)
+    try:
+        big = 2 * size
+        good = _keys(3)
+        gdata = _u8_pattern(3 * big, seed=size + 1)
+        _put_u8(conn, good, big, gdata)
+        short = _keys(1)
+        _put_u8(conn, short, size, _u8_pattern(size, seed=size + 2))
+        for order in ([good[0], good[1], short[0], good[2]], short + good, good + short):
+            dst = _sentinel_dst(conn, 4 * big)
+            with pytest.raises(Exception, match=INVALID_REQ):
+                conn.read_cache(dst, [(k, i * big) for i, k in enumerate(order)], big)
+            assert bool((dst == SENTINEL).all())
+        dst = _sentinel_dst(conn, 4 * big)
+        conn.read_cache(dst, [(k, i * big) for i, k in enumerate(good)], big)
+        conn.sync()
+        assert torch.equal(dst[: 3 * big], gdata)
+        assert bool((dst[3 * big:] == SENTINEL).all())
+    finally:
+        conn.close()
+
+
+@pytest.mark.parametrize("size", READ_SIZE_KEYS)
+def test_read_size_after_a_larger_rewrite_of_the_key(read_size_server, size):
+    """Dedup is first-write-wins at any size: the second writer of a key, with
+    a page twice as large, gets the FAKE block, and its own read at its own
+    size is refused; the first writer's bytes stay readable."""
+    conn = make_client(read_size_server)
+    try:
+        keys = _keys(4)
+        first = _u8_pattern(4 * size, seed=size + 3)
+        _put_u8(conn, keys, size, first)
+        second = _u8_pattern(2 * size, seed=size + 4)
+        blocks2 = _put_u8(conn, keys[:1], 2 * size, second)
+        assert tuple(blocks2[0]) == (0, 0)
+        dst = _sentinel_dst(conn, 2 * size)
+        with pytest.raises(Exception, match=INVALID_REQ):
+            conn.read_cache(dst, [(keys[0], 0)], 2 * size)
+        assert bool((dst == SENTINEL).all())
+        conn.read_cache(dst, [(keys[0], 0)], size)
+        conn.sync()
+        assert torch.equal(dst[:size], first[:size])
+        assert bool((dst[size:] == SENTINEL).all())
+    finally:
+        conn.close()
+
+
+def test_read_size_refused_before_a_streamed_response(read_size_server):
+    """A 40 MiB single-shard response streams in 16 MiB segments. A short
+    entry in the LAST segment must refuse the read before the first segment
+    is on the wire: the client sees INVALID_REQ, not a torn payload, and the
+    connection's framing survives."""
+    conn = make_client(read_size_server)
+    try:
+        page, n = 128 << 10, 320  # 40 MiB
+        keys = _keys(n)
+        data = _u8_pattern(n * page, seed=40)
+        _put_u8(conn, keys[:-1], page, data)
+        _put_u8(conn, keys[-1:], page // 2, data[(n - 1) * page:])
+        offs = [i * page for i in range(n)]
+        dst = _sentinel_dst(conn, n * page)
+        with pytest.raises(Exception, match=INVALID_REQ):
+            conn.read_cache(dst, list(zip(keys, offs)), page)
+        assert bool((dst == SENTINEL).all())
+        # same connection: the streamed path with the good keys only, and the
+        # short key at its own size
+        conn.read_cache(dst, list(zip(keys[:-1], offs)), page)
+        conn.read_cache(dst, [(keys[-1], offs[-1])], page // 2)
+        conn.sync()
+        assert torch.equal(dst[: (n - 1) * page + page // 2], data[: (n - 1) * page + page // 2])
+        assert bool((dst[(n - 1) * page + page // 2:] == SENTINEL).all())
+    finally:
+        conn.close()

@@ -211,6 +211,78 @@ def test_verbs_extended_arena_registered(ports):
         ifs.unregister_server()
 
 
+@pytest.mark.parametrize("size", [1000, 16384, 16400])
+def test_verbs_read_sizes(cpu_server, size):
+    """The WR of a served read takes its length from the request: a page of at
+    most the stored size returns that prefix, a larger one is answered with an
+    INVALID_REQ error IMM (fast, no timeout) and nothing is written; the
+    connection keeps serving. The key sits first in a run of four, so a server
+    without the rule would have copied the neighbour's bytes."""
+    import time
+
+    conn = verbs_client(cpu_server)
+    try:
+        run = uuid.uuid4().hex[:8]
+        keys = [f"vs-{run}-{i}" for i in range(4)]
+        src = torch.randint(0, 255, (4 * size,), dtype=torch.uint8,
+                            generator=torch.Generator().manual_seed(size))
+        src[src == 0xA5] = 255
+        conn.register_mr(src)
+        blocks = conn.allocate_rdma(keys, size)
+        conn.rdma_write_cache(src, [i * size for i in range(4)], size, blocks)
+        conn.sync()
+        for page in (size, size - 1, size // 2):
+            dst = torch.full((2 * size + 16,), 0xA5, dtype=torch.uint8)
+            conn.register_mr(dst)
+            conn.read_cache(dst, [(keys[0], 0)], page)
+            conn.sync()
+            assert torch.equal(dst[:page], src[:page]), page
+            assert bool((dst[page:] == 0xA5).all()), page
+        for page in (size + 1, 2 * size):
+            dst = torch.full((2 * size + 16,), 0xA5, dtype=torch.uint8)
+            conn.register_mr(dst)
+            t0 = time.time()
+            with pytest.raises(Exception, match="-400"):
+                conn.read_cache(dst, [(keys[0], 0)], page)
+                conn.sync()
+            assert time.time() - t0 < 5.0, "refused via the error IMM, not a timeout"
+            assert bool((dst == 0xA5).all()), page
+            conn.read_cache(dst, [(keys[0], 0)], size)
+            conn.sync()
+            assert torch.equal(dst[:size], src[:size])
+            assert bool((dst[size:] == 0xA5).all())
+    finally:
+        conn.close()
+
+
+def test_verbs_reregistered_address_uses_the_newest_region(cpu_server):
+    """Registered regions are never dropped, so an address can be registered
+    twice: first for a short tensor, later for a longer one that the allocator
+    placed there. The lookup must take the newest region; with the oldest, the
+    second page below lies past the stale region's end and its WR fails the
+    provider's bounds check. Deterministic: both registrations are views of one
+    buffer, so the address is the same by construction."""
+    conn = verbs_client(cpu_server)
+    try:
+        page = 4096  # bytes
+        buf = torch.zeros(4 * page, dtype=torch.uint8)
+        conn.register_mr(buf[:page])  # the "freed" short tensor at this address
+        conn.register_mr(buf)  # the live, longer one
+        src = torch.randint(1, 255, (2 * page,), dtype=torch.uint8,
+                            generator=torch.Generator().manual_seed(11))
+        buf[: 2 * page] = src
+        run = uuid.uuid4().hex[:8]
+        keys = [f"vr-{run}-{i}" for i in range(2)]
+        blocks = conn.allocate_rdma(keys, page)
+        conn.rdma_write_cache(buf, [0, page], page, blocks)  # page 1 is past the stale end
+        conn.sync()
+        conn.read_cache(buf, [(keys[0], 2 * page), (keys[1], 3 * page)], page)
+        conn.sync()
+        assert torch.equal(buf[2 * page:], src)
+    finally:
+        conn.close()
+
+
 def test_verbs_missing_key(cpu_server):
     """The server answers a read of a missing key with an error IMM; the
     client must fail FAST (not wait out its 10 s CQ timeout)."""
