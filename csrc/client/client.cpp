@@ -401,9 +401,12 @@ int ClientConn::rw_local_packed(char op, const char* keys_blob, size_t blob_len,
                                 uint64_t* out_ticket, uint32_t extra_flags,
                                 uint32_t n_segments, uint64_t segment_stride,
                                 const PackedLocalSliceExt* slice,
-                                const PackedLocalTensorExt* tset) {
+                                const PackedLocalTensorExt* tset,
+                                const PackedLocalPermExt* perm) {
     if (out_ticket) *out_ticket = 0;  // 0 = completed synchronously
     if (!connected_) return -1;
+    if (perm && perm->rows != 0 && ((slice && slice->n_pieces != 0) || tset))
+        return -INVALID_REQ;  // not together
     if (slice && slice->n_pieces != 0 && op != 'R') return -INVALID_REQ;  // read-only
     if (slice && slice->n_pieces != 0 && tset) return -INVALID_REQ;  // not together
     if (!gpu::available()) {
@@ -458,7 +461,8 @@ int ClientConn::rw_local_packed(char op, const char* keys_blob, size_t blob_len,
     memcpy(h.ipc, handle.bytes, gpu::kIpcHandleSize);
 
     std::vector<uint8_t> body =
-        build_packed_local(h, n_segments, segment_stride, offsets, keys_blob, blob_len, slice, tset);
+        build_packed_local(h, n_segments, segment_stride, offsets, keys_blob, blob_len, slice,
+                           tset, perm);
 
     char wire_op = (op == 'W') ? OP_W_FAST : OP_R_FAST;
     static const bool dbg = getenv("IFS_CLIENT_DEBUG") != nullptr;

@@ -76,7 +76,12 @@ class ClientConn {
                         uint64_t* out_ticket = nullptr, uint32_t extra_flags = 0,
                         uint32_t n_segments = 1, uint64_t segment_stride = 0,
                         const PackedLocalSliceExt* slice = nullptr,
-                        const PackedLocalTensorExt* tset = nullptr);
+                        const PackedLocalTensorExt* tset = nullptr,
+                        const PackedLocalPermExt* perm = nullptr);
+    // perm (null or rows == 0: not permuted): the tensor holds every page's
+    // pieces with two axes exchanged (permuted pages, core/page_codec.h). With
+    // a slice or a tensor set as well it returns -INVALID_REQ without sending
+    // anything.
     // Tensor sets (docs/design.md, "tensor sets"): register the tensors at
     // ptrs[g] (extents[g] bytes each, all on device_id) as one ordered set on
     // this connection; returns the set id (> 0) or a negative status. A

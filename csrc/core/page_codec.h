@@ -219,4 +219,57 @@ inline PageSlice slice_from_wire(const PackedLocalSliceExt& e) {
     return {e.n_pieces, e.page_bytes, e.offset, e.piece_bytes, e.stride};
 }
 
+// Permuted pages (docs/design.md, "permuted pages"): on the CLIENT side of a
+// request a page may hold its pieces in the other order of two axes. A page is
+// outer * rows * cols pieces of piece_bytes LOGICAL bytes; piece (o, r, c)
+// starts at logical byte ((o*rows + r)*cols + c) * piece_bytes of the STORED
+// (canonical) page and at ((o*cols + c)*rows + r) * piece_bytes of the client
+// page, to which PageSegments then apply as to any page. For a KV block,
+// outer = 2, rows = T, cols = H and the piece is one head of one token: the
+// store keeps [2, T, H, hd] whether the engine's cache is that or [2, H, T, hd].
+// The bound is a condition, not a tuning value: it keeps every piece index,
+// and the products of two of them that the kernels form, inside 32 bits.
+constexpr uint32_t kMaxPermPieces = 1u << 20;
+
+// Client-side piece order of a request's pages; rows == 0 (the default) is
+// "not permuted".
+struct PagePermute {
+    uint32_t outer = 0, rows = 0, cols = 0;
+    uint64_t piece_bytes = 0;
+};
+
+inline bool permute_is_set(const PagePermute& p) { return p.rows != 0; }
+
+// The one predicate for a permuted page (wire parser, server, shard,
+// launchers, bindings, Python client). The pieces tile the page exactly. A
+// transforming kernel moves whole 8-element lane units and, for mxfp4, whole
+// 32-element groups: the piece is a multiple of the codec's page multiple. A
+// piece never straddles a client segment, and the page obeys segments_legal
+// like any other. rows == 1 or cols == 1 is legal: it is the identity.
+inline bool permute_legal(PageCodec c, size_t page_bytes, const PagePermute& p,
+                          const PageSegments& seg = {}) {
+    if (p.outer < 1 || p.rows < 1 || p.cols < 1 || p.piece_bytes == 0) return false;
+    // 128-bit products: three 32-bit counts and a 64-bit size off the wire
+    // must not wrap into a match.
+    using u128 = unsigned __int128;
+    const u128 pieces = static_cast<u128>(p.outer) * p.rows * p.cols;
+    if (pieces > kMaxPermPieces) return false;
+    if (pieces * p.piece_bytes != static_cast<u128>(page_bytes)) return false;
+    if (page_codec_transforms(c) && p.piece_bytes % page_codec_info(c).page_multiple != 0)
+        return false;
+    if (seg.n != 1) {
+        if (seg.n == 0 || static_cast<uint64_t>(pieces) % seg.n != 0) return false;
+        if (!segments_legal(c, page_bytes, seg.n, seg.stride_bytes)) return false;
+    }
+    return true;
+}
+
+// The geometry as the wire extension carries it, and back.
+inline PackedLocalPermExt permute_to_wire(const PagePermute& p) {
+    return {p.outer, p.rows, p.cols, 0, p.piece_bytes};
+}
+inline PagePermute permute_from_wire(const PackedLocalPermExt& e) {
+    return {e.outer, e.rows, e.cols, e.piece_bytes};
+}
+
 }  // namespace ifs

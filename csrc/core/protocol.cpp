@@ -162,16 +162,20 @@ std::vector<uint8_t> build_packed_local(PackedLocalHdr h, uint32_t n_segments,
                                         uint64_t segment_stride, const uint64_t* offsets,
                                         const char* keys_blob, size_t blob_len,
                                         const PackedLocalSliceExt* slice,
-                                        const PackedLocalTensorExt* tset) {
+                                        const PackedLocalTensorExt* tset,
+                                        const PackedLocalPermExt* perm) {
     const size_t n = h.n_blocks;
     const bool seg = n_segments != 1;
     const bool sliced = slice && slice->n_pieces != 0;
     if (seg) h.flags |= kLocalFlagSegmented;
     if (sliced) h.flags |= kLocalFlagSliced;
     if (tset) h.flags |= kLocalFlagTensorSet;
+    const bool permuted = perm && perm->rows != 0;
+    if (permuted) h.flags |= kLocalFlagPermuted;
     const size_t seg_ext = seg ? sizeof(PackedLocalSegExt) : 0;
     const size_t slice_end = seg_ext + (sliced ? sizeof(PackedLocalSliceExt) : 0);
-    const size_t ext = slice_end + (tset ? sizeof(PackedLocalTensorExt) : 0);
+    const size_t tset_end = slice_end + (tset ? sizeof(PackedLocalTensorExt) : 0);
+    const size_t ext = tset_end + (permuted ? sizeof(PackedLocalPermExt) : 0);
     std::vector<uint8_t> body(sizeof(h) + ext + n * 8 + blob_len);
     memcpy(body.data(), &h, sizeof(h));
     if (seg) {
@@ -180,6 +184,7 @@ std::vector<uint8_t> build_packed_local(PackedLocalHdr h, uint32_t n_segments,
     }
     if (sliced) memcpy(body.data() + sizeof(h) + seg_ext, slice, sizeof(*slice));
     if (tset) memcpy(body.data() + sizeof(h) + slice_end, tset, sizeof(*tset));
+    if (permuted) memcpy(body.data() + sizeof(h) + tset_end, perm, sizeof(*perm));
     if (n) memcpy(body.data() + sizeof(h) + ext, offsets, n * 8);
     if (blob_len) memcpy(body.data() + sizeof(h) + ext + n * 8, keys_blob, blob_len);
     return body;
@@ -196,6 +201,8 @@ bool parse_packed_local(char op, const uint8_t* body, size_t body_len, PackedLoc
     // been read, by tensors_legal.
     const bool has_tset = (h.flags & kLocalFlagTensorSet) != 0;
     if (has_tset && (h.flags & kLocalFlagSliced)) return false;
+    const bool permuted = (h.flags & kLocalFlagPermuted) != 0;
+    if (permuted && (h.flags & (kLocalFlagSliced | kLocalFlagTensorSet))) return false;
     if (h.flags & kLocalFlagSegmented) {
         if (body_len < pos + sizeof(PackedLocalSegExt)) return false;
         PackedLocalSegExt e;
@@ -239,6 +246,22 @@ bool parse_packed_local(char op, const uint8_t* body, size_t body_len, PackedLoc
                            e.n_tensors))
             return false;
         out->tset = e;
+    }
+    out->perm = PackedLocalPermExt{};
+    if (permuted) {
+        if (body_len < pos + sizeof(PackedLocalPermExt)) return false;
+        PackedLocalPermExt e;
+        memcpy(&e, body + pos, sizeof(e));
+        pos += sizeof(e);
+        if (e.rsvd != 0) return false;
+        PageCodec codec = PageCodec::kNone;
+        if (op == OP_W_FAST && !page_codec_from_flags(h.flags, &codec)) return false;
+        // rows == 0 fails permute_legal: a parsed request is permuted exactly
+        // when rows != 0.
+        if (!permute_legal(codec, h.block_size, permute_from_wire(e),
+                           PageSegments{out->n_segments, out->segment_stride}))
+            return false;
+        out->perm = e;
     }
     const size_t n = h.n_blocks;
     const size_t off_end = pos + n * 8;

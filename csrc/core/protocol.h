@@ -57,7 +57,8 @@ constexpr char OP_STATS = 'Q';    // server stats JSON over the wire (extension)
 // flatbuffers LocalMetaRequest ops remain accepted for wire compatibility.
 // Body: PackedLocalHdr, [PackedLocalSegExt when kLocalFlagSegmented is set,]
 // [PackedLocalSliceExt when kLocalFlagSliced is set,] [PackedLocalTensorExt
-// when kLocalFlagTensorSet is set,] u64 offsets[n], NUL-separated key bytes
+// when kLocalFlagTensorSet is set,] [PackedLocalPermExt when
+// kLocalFlagPermuted is set,] u64 offsets[n], NUL-separated key bytes
 // (n keys).
 constexpr char OP_W_FAST = 'w';
 constexpr char OP_R_FAST = 'r';
@@ -133,6 +134,20 @@ struct PackedLocalTensorExt {
 #pragma pack(pop)
 static_assert(sizeof(PackedLocalTensorExt) == 16, "packed local tensor-set extension size");
 
+// Follows PackedLocalHdr and every other extension when kLocalFlagPermuted is
+// set: the order of the pieces of the request's pages in CLIENT memory
+// (core/page_codec.h, PagePermute; docs/design.md, "permuted pages").
+#pragma pack(push, 1)
+struct PackedLocalPermExt {
+    uint32_t outer;
+    uint32_t rows;
+    uint32_t cols;
+    uint32_t rsvd;         // 0
+    uint64_t piece_bytes;  // logical bytes; outer * rows * cols pieces are block_size
+};
+#pragma pack(pop)
+static_assert(sizeof(PackedLocalPermExt) == 24, "packed local permute extension size");
+
 // OP_TSET_REGISTER body: this header, then n_tensors records in set order.
 #pragma pack(push, 1)
 struct PackedTensorSetHdr {
@@ -176,6 +191,11 @@ constexpr uint32_t kLocalFlagSliced = 16;
 // PackedLocalTensorExt that follows the other extensions (extension; both
 // packed ops). Together with kLocalFlagSliced it is INVALID_REQ.
 constexpr uint32_t kLocalFlagTensorSet = 32;
+// The client holds each page with two piece axes exchanged, as the
+// PackedLocalPermExt after the other extensions says (extension; both packed
+// ops). The stored block is the canonical page's. Together with
+// kLocalFlagSliced or kLocalFlagTensorSet it is INVALID_REQ.
+constexpr uint32_t kLocalFlagPermuted = 64;
 
 std::string op_name(char op);
 
@@ -252,7 +272,10 @@ std::vector<uint8_t> build_packed_local(PackedLocalHdr h, uint32_t n_segments,
                                         uint64_t segment_stride, const uint64_t* offsets,
                                         const char* keys_blob, size_t blob_len,
                                         const PackedLocalSliceExt* slice = nullptr,
-                                        const PackedLocalTensorExt* tset = nullptr);
+                                        const PackedLocalTensorExt* tset = nullptr,
+                                        const PackedLocalPermExt* perm = nullptr);
+// (The permute extension and kLocalFlagPermuted are written only for a `perm`
+// with rows != 0, its rsvd as given.)
 // (The tensor-set extension and kLocalFlagTensorSet are written only when
 // `tset` is given; the segment extension is then written for n_segments > 1
 // as always, n_segments being the total over all tensors.)
@@ -274,6 +297,7 @@ struct PackedLocalReq {
     PackedLocalSliceExt slice{};  // n_pieces == 0: whole pages
     bool has_tset = false;
     PackedLocalTensorExt tset{};
+    PackedLocalPermExt perm{};  // rows == 0: not permuted
     std::vector<std::pair<std::string_view, uint64_t>> blocks;
 };
 // False (the server answers INVALID_REQ) for a truncated body or extension,
@@ -285,7 +309,9 @@ struct PackedLocalReq {
 // piece_bytes or slice_legal refuses the geometry under plain rules. With
 // kLocalFlagTensorSet the geometry rule is tensors_legal instead of
 // segments_legal (same codec choice), and the flag together with
-// kLocalFlagSliced is refused.
+// kLocalFlagSliced is refused. kLocalFlagPermuted is refused next to either
+// of those two flags, and when permute_legal refuses the geometry for
+// block_size (same codec choice as for segments).
 bool parse_packed_local(char op, const uint8_t* body, size_t body_len, PackedLocalReq* out);
 
 // Sentinel for duplicate-key allocations: the server returns rkey=0, addr=0

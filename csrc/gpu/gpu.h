@@ -188,6 +188,33 @@ bool launch_load_sliced(int dev, Stream s, PageCodec codec, const uint64_t* dev_
 // edges of the lane mapping from it.
 constexpr int kSliceThreads = 512;
 
+// --- permuted pages -----------------------------------------------------------
+// The CLIENT side of every page (source of kStore, destination of kLoad)
+// holds the page's pieces with two axes exchanged (core/page_codec.h,
+// PagePermute; docs/design.md, "permuted pages"), and is split into seg.n
+// segments on top of that when seg.n > 1; the stored block is byte-identical
+// to the one the contiguous kernels make of the canonical page. Descriptors
+// are what they are elsewhere (device-visible pointers); the geometry rides in
+// the kernel arguments. Plain pages: the 16 B/lane kernel when aligned16 holds
+// (every descriptor pointer is a multiple of 16; the CALLER checks) and the
+// piece and, where one is applied, the client stride are multiples of 16 too;
+// else the byte kernel. False before any launch for a geometry permute_legal
+// refuses or a grid that does not fit.
+bool launch_copy_blocks_perm(int dev, Stream s, const uint64_t* dev_src, const uint64_t* dev_dst,
+                             int n_blocks, size_t bytes_per_block, bool aligned16,
+                             PageSegments seg, PageDir dir, PagePermute perm);
+// Transforming codecs, scales as for launch_transform_blocks: fp8 keeps ONE
+// scale per page, mxfp4 indexes codes and scale bytes by the page-global
+// STORED unit. There is no byte fallback: additionally false, before any
+// launch, unless aligned16 holds.
+bool launch_transform_blocks_perm(int dev, Stream s, PageCodec codec, PageDir dir,
+                                  const uint64_t* dev_src, const uint64_t* dev_dst,
+                                  float* dev_scales, int n_blocks, size_t elems_per_block,
+                                  bool aligned16, PageSegments seg, PagePermute perm);
+// Workgroup size of the six permute kernels, public so that tests compute the
+// edges of the lane mapping from it.
+constexpr int kPermThreads = 512;
+
 // --- block fingerprint ------------------------------------------------------
 // 64-bit position-salted fingerprint per block -> out_hashes[i] (device mem).
 bool launch_hash_blocks(int dev, Stream s, const uint64_t* dev_ptrs, int n_blocks,

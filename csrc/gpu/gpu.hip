@@ -1419,6 +1419,386 @@ bool launch_load_sliced(int dev, Stream stream, PageCodec codec, const uint64_t*
     return true;
 }
 
+// --- permuted pages ------------------------------------------------------------
+// The client holds a page's outer * rows * cols pieces with the two inner axes
+// exchanged (gpu.h, docs/design.md "permuted pages"): piece (o, r, c) is piece
+// (o*rows + r)*cols + c of the stored page and piece (o*cols + c)*rows + r of
+// the client page. A piece is one head of one token (128-512 B), so the lane
+// mapping is the sliced kernels': L, the smallest power of two >= units per
+// piece (capped at the workgroup), lanes share a piece, threadIdx.x >>
+// lane_shift picks the piece of a step and threadIdx.x & (L - 1) the unit
+// lane, which strides by L inside the piece.
+//
+// Pieces are walked in the DESTINATION's order (stored order for kStore,
+// client order for kLoad): neighbouring lane groups then write neighbouring
+// pieces, a wave's stores are contiguous, and the strided side is the loads,
+// which the memory system reorders more freely than partial-line writes. The
+// outer axis is not permuted, so it goes into the grid: a workgroup is (block,
+// o, chunk) and walks plane o only. Inside a plane the destination index d
+// splits as d = hi * inner + lo by ONE division by the workgroup-uniform inner
+// extent (cols for kStore, rows for kLoad), and the same piece's index in the
+// source's order is lo * other + hi. Nothing in the unit loop divides. The
+// client address of a piece is found as for slices: its client index over
+// pieces_per_seg gives the segment and the place inside it.
+struct PermArgs {
+    uint32_t outer, rows, cols;
+    uint32_t chunks;          // workgroups per (block, o) plane
+    uint32_t lane_shift;      // log2(L)
+    uint32_t pieces_per_seg;  // outer * rows * cols / client segments
+    uint32_t n_segs;          // client segments
+    uint32_t to_pool;         // 1: client -> stored block, 0: stored block -> client
+    uint64_t units;           // per piece, in the kernel's unit
+    uint64_t piece_bytes;     // logical
+    uint64_t seg_stride;      // client bytes from one segment to the next
+    uint64_t page_bytes;      // logical
+};
+
+// Walks the steps first_step, first_step + step_stride, ... of plane o;
+// move(stored piece index, client byte offset of the piece, lane, L) runs one
+// piece's unit loop. All piece indices are below kMaxPermPieces, so every
+// product of an index and an extent here fits 32 bits.
+template <typename Move>
+__device__ __forceinline__ void perm_walk_plane(const PermArgs& a, uint32_t o,
+                                                uint32_t first_step, uint32_t step_stride,
+                                                Move move) {
+    const uint32_t L = 1u << a.lane_shift;
+    const uint32_t per_step = blockDim.x >> a.lane_shift;
+    const uint32_t lane = threadIdx.x & (L - 1);
+    const uint32_t plane = a.rows * a.cols;
+    const uint32_t inner = a.to_pool ? a.cols : a.rows;
+    const uint32_t other = a.to_pool ? a.rows : a.cols;
+    for (uint32_t d = first_step * per_step + (threadIdx.x >> a.lane_shift); d < plane;
+         d += step_stride * per_step) {
+        uint32_t hi = d / inner;
+        uint32_t lo = d - hi * inner;
+        uint32_t t = lo * other + hi;  // the piece's index in the source's order
+        uint32_t stored = o * plane + (a.to_pool ? d : t);
+        uint32_t client = o * plane + (a.to_pool ? t : d);
+        uint32_t sg = client / a.pieces_per_seg;
+        uint32_t r = client - sg * a.pieces_per_seg;
+        move(stored, sg * a.seg_stride + r * a.piece_bytes, lane, L);
+    }
+}
+
+// The prologue of the five (block, o, chunk) kernels: decodes the triple once,
+// reads block b's descriptor pair once through LDS as block_chunk_descs does,
+// and hands out the pool and client base addresses whichever way the copy
+// runs. Returns the chunk.
+__device__ __forceinline__ uint32_t perm_block_plane_chunk(const uint64_t* __restrict__ src_ptrs,
+                                                           const uint64_t* __restrict__ dst_ptrs,
+                                                           const PermArgs& a, uint32_t* b,
+                                                           uint32_t* o, uint64_t* pool,
+                                                           uint64_t* client) {
+    const uint32_t per_block = a.outer * a.chunks;
+    *b = blockIdx.x / per_block;
+    const uint32_t r = blockIdx.x - *b * per_block;
+    *o = r / a.chunks;
+    __shared__ uint64_t lds[2];
+    if (threadIdx.x == 0) {
+        lds[0] = src_ptrs[*b];
+        lds[1] = dst_ptrs[*b];
+    }
+    __syncthreads();
+    *pool = a.to_pool ? lds[1] : lds[0];
+    *client = a.to_pool ? lds[0] : lds[1];
+    return r - *o * a.chunks;
+}
+
+// plain, 16 bytes per lane: pointers, piece and client stride are 16-byte
+// multiples (the launcher picks the byte kernel otherwise).
+__global__ void copy_blocks_vec_perm_kernel(const uint64_t* __restrict__ src_ptrs,
+                                            const uint64_t* __restrict__ dst_ptrs, PermArgs a) {
+    uint32_t b, o;
+    uint64_t pool, client;
+    uint32_t chunk = perm_block_plane_chunk(src_ptrs, dst_ptrs, a, &b, &o, &pool, &client);
+    perm_walk_plane(a, o, chunk, a.chunks,
+                    [&](uint32_t stored, uint64_t coff, uint32_t lane, uint32_t L) {
+                        const uint64_t p = pool + stored * a.piece_bytes, c = client + coff;
+                        const uint4* s4 = reinterpret_cast<const uint4*>(a.to_pool ? c : p);
+                        uint4* d4 = reinterpret_cast<uint4*>(a.to_pool ? p : c);
+                        for (uint64_t u = lane; u < a.units; u += L) d4[u] = s4[u];
+                    });
+}
+
+__global__ void copy_blocks_byte_perm_kernel(const uint64_t* __restrict__ src_ptrs,
+                                             const uint64_t* __restrict__ dst_ptrs, PermArgs a) {
+    uint32_t b, o;
+    uint64_t pool, client;
+    uint32_t chunk = perm_block_plane_chunk(src_ptrs, dst_ptrs, a, &b, &o, &pool, &client);
+    perm_walk_plane(a, o, chunk, a.chunks,
+                    [&](uint32_t stored, uint64_t coff, uint32_t lane, uint32_t L) {
+                        const uint64_t p = pool + stored * a.piece_bytes, c = client + coff;
+                        const uint8_t* s1 = reinterpret_cast<const uint8_t*>(a.to_pool ? c : p);
+                        uint8_t* d1 = reinterpret_cast<uint8_t*>(a.to_pool ? p : c);
+                        for (uint64_t u = lane; u < a.units; u += L) d1[u] = s1[u];
+                    });
+}
+
+// fp8 quantize: one 512-thread workgroup per page and two passes, because the
+// scale is the PAGE's. The absmax does not depend on the order of the
+// elements, so pass 1 reads the client page linearly, segment by segment, as
+// the segmented kernel does. Pass 2 permutes: plane by plane in stored order,
+// 8 bf16 in (uint4) -> 8 codes out (uint2) per lane; stored byte = logical
+// element index, so a piece's codes start at stored * piece_bytes / 2.
+__global__ void quant_blocks_bf16_fp8_perm_kernel(const uint64_t* __restrict__ src_ptrs,
+                                                  const uint64_t* __restrict__ dst_ptrs,
+                                                  float* __restrict__ scales, PermArgs a) {
+    const uint64_t src = src_ptrs[blockIdx.x];
+    const uint64_t dst = dst_ptrs[blockIdx.x];
+    __shared__ uint32_t red[8];  // 512 threads / 64-wide wavefronts
+    __shared__ float scale_sh;
+    uint32_t m = 0;  // largest finite bf16 magnitude, as bits
+    const uint64_t seg16 = a.pieces_per_seg * a.piece_bytes / 16;
+    for (uint32_t sg = 0; sg < a.n_segs; sg++) {
+        const uint4* src4 = reinterpret_cast<const uint4*>(src + sg * a.seg_stride);
+        for (uint64_t u = threadIdx.x; u < seg16; u += blockDim.x) {
+            uint4 pk = src4[u];
+            const uint16_t* h = reinterpret_cast<const uint16_t*>(&pk);
+#pragma unroll
+            for (int i = 0; i < 8; i++) m = fp8::absmax_step(m, h[i]);
+        }
+    }
+    for (int off = 32; off; off >>= 1) m = max(m, __shfl_down(m, off, 64));
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t mm = red[0];
+        for (int w = 1; w < static_cast<int>(blockDim.x) / 64; w++) mm = max(mm, red[w]);
+        scale_sh = fp8::scale_from_absmax_bits(mm);
+        scales[blockIdx.x] = scale_sh;
+    }
+    __syncthreads();
+    const float inv = 1.f / scale_sh;
+    for (uint32_t o = 0; o < a.outer; o++)
+        perm_walk_plane(a, o, 0, 1, [&](uint32_t stored, uint64_t coff, uint32_t lane, uint32_t L) {
+            const uint4* s4 = reinterpret_cast<const uint4*>(src + coff);
+            uint2* d2 = reinterpret_cast<uint2*>(dst + stored * a.piece_bytes / kPageElemBytes);
+            for (uint64_t u = lane; u < a.units; u += L) {
+                uint4 pk = s4[u];
+                const uint16_t* h = reinterpret_cast<const uint16_t*>(&pk);
+                uint8_t out[8];
+#pragma unroll
+                for (int i = 0; i < 8; i++) {
+                    float f = fp8::bits_f32(static_cast<uint32_t>(h[i]) << 16);
+                    out[i] = fp8::f32_to_e4m3(f * inv);
+                }
+                d2[u] = *reinterpret_cast<const uint2*>(out);
+            }
+        });
+}
+
+// fp8 dequantize: nothing needs a page-wide pass, so the mapping is the
+// copy's, with block b's scale in scales[b]. 8 codes in (uint2) -> 8 bf16 out
+// (uint4) per lane.
+__global__ void dequant_blocks_fp8_bf16_perm_kernel(const uint64_t* __restrict__ src_ptrs,
+                                                    const uint64_t* __restrict__ dst_ptrs,
+                                                    const float* __restrict__ scales,
+                                                    PermArgs a) {
+    uint32_t b, o;
+    uint64_t pool, client;
+    uint32_t chunk = perm_block_plane_chunk(src_ptrs, dst_ptrs, a, &b, &o, &pool, &client);
+    const float scale = scales[b];
+    perm_walk_plane(a, o, chunk, a.chunks,
+                    [&](uint32_t stored, uint64_t coff, uint32_t lane, uint32_t L) {
+                        const uint2* s2 = reinterpret_cast<const uint2*>(
+                            pool + stored * a.piece_bytes / kPageElemBytes);
+                        uint4* d4 = reinterpret_cast<uint4*>(client + coff);
+                        for (uint64_t u = lane; u < a.units; u += L) {
+                            uint2 pk = s2[u];
+                            const uint8_t* c = reinterpret_cast<const uint8_t*>(&pk);
+                            uint16_t out[8];
+#pragma unroll
+                            for (int i = 0; i < 8; i++) out[i] = fp8::decode_to_bf16(c[i], scale);
+                            d4[u] = *reinterpret_cast<const uint4*>(out);
+                        }
+                    });
+}
+
+// mxfp4: codes and scale bytes are indexed by the page-global STORED unit
+// g = stored * units + u: the lane's 8 codes are the 4 bytes at codes[g], the
+// group's scale byte sits behind all codes at page_elems / 2 + (g >> 2).
+// The quantizer's cross-lane steps need the four lanes of a quad to hold the
+// four units of ONE 32-element group and to run the loop body together. A
+// piece is whole groups (permute_legal), so units % 4 == 0 and L, a power of
+// two >= units, is >= 4: lane_shift >= 2, the four lanes 4k..4k+3 share
+// threadIdx.x >> lane_shift and therefore the piece, and their unit lanes
+// threadIdx.x & (L - 1) are 4j..4j+3. u advances by L, a multiple of 4, and
+// units is one too, so in every iteration the quad holds units 4j'..4j'+3 of
+// its piece, all four below `units` or none; stored * units is a multiple of
+// 4, so g and u agree in their low two bits. __shfl_xor by 1 and 2 thus stays
+// inside the group, and exactly the lane with (u & 3) == 0 writes the scale.
+__global__ void quant_blocks_bf16_mxfp4_perm_kernel(const uint64_t* __restrict__ src_ptrs,
+                                                    const uint64_t* __restrict__ dst_ptrs,
+                                                    PermArgs a) {
+    uint32_t b, o;
+    uint64_t pool, client;
+    uint32_t chunk = perm_block_plane_chunk(src_ptrs, dst_ptrs, a, &b, &o, &pool, &client);
+    uint8_t* scales = reinterpret_cast<uint8_t*>(pool) + a.page_bytes / kPageElemBytes / 2;
+    perm_walk_plane(
+        a, o, chunk, a.chunks, [&](uint32_t stored, uint64_t coff, uint32_t lane, uint32_t L) {
+            const uint64_t g0 = stored * a.units;
+            const uint4* s4 = reinterpret_cast<const uint4*>(client + coff);
+            uint32_t* codes = reinterpret_cast<uint32_t*>(pool) + g0;
+            for (uint64_t u = lane; u < a.units; u += L) {
+                uint4 pk = s4[u];
+                const uint16_t* h = reinterpret_cast<const uint16_t*>(&pk);
+                uint32_t key = 0;
+#pragma unroll
+                for (int i = 0; i < 8; i++) key = mxfp4::key_step(key, h[i]);
+                key = max(key, __shfl_xor(key, 1, 64));
+                key = max(key, __shfl_xor(key, 2, 64));
+                uint8_t E = mxfp4::group_exponent(key);
+                uint32_t out = 0;
+#pragma unroll
+                for (int i = 0; i < 8; i++)
+                    out |= static_cast<uint32_t>(mxfp4::encode(h[i], E)) << (4 * i);
+                codes[u] = out;
+                if ((u & 3u) == 0) scales[(g0 + u) >> 2] = E;
+            }
+        });
+}
+
+// Decoding is lane-local: no quad has to run together here.
+__global__ void dequant_blocks_mxfp4_bf16_perm_kernel(const uint64_t* __restrict__ src_ptrs,
+                                                      const uint64_t* __restrict__ dst_ptrs,
+                                                      PermArgs a) {
+    uint32_t b, o;
+    uint64_t pool, client;
+    uint32_t chunk = perm_block_plane_chunk(src_ptrs, dst_ptrs, a, &b, &o, &pool, &client);
+    const uint8_t* scales =
+        reinterpret_cast<const uint8_t*>(pool) + a.page_bytes / kPageElemBytes / 2;
+    perm_walk_plane(
+        a, o, chunk, a.chunks, [&](uint32_t stored, uint64_t coff, uint32_t lane, uint32_t L) {
+            const uint64_t g0 = stored * a.units;
+            const uint32_t* codes = reinterpret_cast<const uint32_t*>(pool) + g0;
+            uint4* d4 = reinterpret_cast<uint4*>(client + coff);
+            for (uint64_t u = lane; u < a.units; u += L) {
+                uint32_t pk = codes[u];
+                uint8_t E = scales[(g0 + u) >> 2];
+                uint16_t out[8];
+#pragma unroll
+                for (int i = 0; i < 8; i++)
+                    out[i] = mxfp4::decode(static_cast<uint8_t>((pk >> (4 * i)) & 0xfu), E);
+                d4[u] = *reinterpret_cast<const uint4*>(out);
+            }
+        });
+}
+
+// What both permute launchers build after their checks: the kernel arguments
+// and the grid of the (block, o, chunk) kernels. `unit` is the bytes of one
+// lane unit. False when that grid does not fit (the fp8 quantizer, one
+// workgroup per page, does not use it: need_grid is false there).
+static bool perm_args(size_t page_bytes, PagePermute perm, PageSegments seg, PageDir dir,
+                      uint64_t unit, int n_blocks, bool need_grid, PermArgs* a, uint32_t* grid) {
+    const uint32_t pieces = perm.outer * perm.rows * perm.cols;  // <= kMaxPermPieces
+    a->outer = perm.outer;
+    a->rows = perm.rows;
+    a->cols = perm.cols;
+    a->units = perm.piece_bytes / unit;
+    a->lane_shift = 0;
+    while ((1ull << a->lane_shift) < a->units && (1 << a->lane_shift) < kPermThreads)
+        a->lane_shift++;
+    const uint32_t per_step = static_cast<uint32_t>(kPermThreads) >> a->lane_shift;
+    const uint64_t plane = static_cast<uint64_t>(perm.rows) * perm.cols;
+    const uint64_t planes = static_cast<uint64_t>(n_blocks) * perm.outer;
+    a->chunks = copy_chunks_per_block((plane + per_step - 1) / per_step, planes, 1);
+    a->pieces_per_seg = pieces / seg.n;
+    a->n_segs = seg.n;
+    a->to_pool = dir == PageDir::kStore;
+    a->piece_bytes = perm.piece_bytes;
+    a->seg_stride = seg.n > 1 ? seg.stride_bytes : 0;
+    a->page_bytes = page_bytes;
+    const uint64_t g = planes * a->chunks;
+    if (need_grid && g > 0x7fffffffull) return false;
+    *grid = static_cast<uint32_t>(g);
+    return true;
+}
+
+bool launch_copy_blocks_perm(int dev, Stream stream, const uint64_t* dev_src,
+                             const uint64_t* dev_dst, int n_blocks, size_t bytes_per_block,
+                             bool aligned16, PageSegments seg, PageDir dir, PagePermute perm) {
+    if (!permute_legal(PageCodec::kNone, bytes_per_block, perm, seg)) {
+        snprintf(g_err, sizeof(g_err), "launch_copy_blocks_perm: illegal page permutation");
+        return false;
+    }
+    if (n_blocks <= 0) return true;
+    const bool vec = aligned16 && perm.piece_bytes % 16 == 0 &&
+                     (seg.n == 1 || seg.stride_bytes % 16 == 0);
+    PermArgs a;
+    uint32_t grid;
+    if (!perm_args(bytes_per_block, perm, seg, dir, vec ? 16 : 1, n_blocks, true, &a, &grid)) {
+        snprintf(g_err, sizeof(g_err), "launch_copy_blocks_perm: grid does not fit");
+        return false;
+    }
+    HIP_OK(hipSetDevice(dev));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (vec)
+        hipLaunchKernelGGL(copy_blocks_vec_perm_kernel, dim3(grid), dim3(kPermThreads), 0, s,
+                           dev_src, dev_dst, a);
+    else
+        hipLaunchKernelGGL(copy_blocks_byte_perm_kernel, dim3(grid), dim3(kPermThreads), 0, s,
+                           dev_src, dev_dst, a);
+    HIP_OK(hipGetLastError());
+    return true;
+}
+
+bool launch_transform_blocks_perm(int dev, Stream stream, PageCodec codec, PageDir dir,
+                                  const uint64_t* dev_src, const uint64_t* dev_dst,
+                                  float* dev_scales, int n_blocks, size_t elems_per_block,
+                                  bool aligned16, PageSegments seg, PagePermute perm) {
+    const char* what = "launch_transform_blocks_perm";
+    const size_t page_bytes = elems_per_block * kPageElemBytes;
+    if (!page_codec_transforms(codec) || elems_per_block == 0 || !page_legal(codec, page_bytes)) {
+        snprintf(g_err, sizeof(g_err), "%s: not a page of a transforming codec", what);
+        return false;
+    }
+    if (!permute_legal(codec, page_bytes, perm, seg)) {
+        snprintf(g_err, sizeof(g_err), "%s: illegal page permutation", what);
+        return false;
+    }
+    if (!aligned16) {
+        snprintf(g_err, sizeof(g_err), "%s: %s needs 16-byte-aligned pointers", what,
+                 page_codec_info(codec).name);
+        return false;
+    }
+    if (page_codec_info(codec).page_scale && !dev_scales) return false;
+    if (n_blocks <= 0) return true;
+    // The transforming kernels' unit is 8 elements: 16 logical bytes.
+    PermArgs a;
+    uint32_t grid;
+    const bool store = dir == PageDir::kStore;
+    if (!perm_args(page_bytes, perm, seg, dir, 16, n_blocks,
+                   !(store && codec == PageCodec::kFp8), &a, &grid)) {
+        snprintf(g_err, sizeof(g_err), "%s: grid does not fit", what);
+        return false;
+    }
+    HIP_OK(hipSetDevice(dev));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const dim3 block(kPermThreads);
+    switch (codec) {
+        case PageCodec::kFp8:
+            if (store)
+                hipLaunchKernelGGL(quant_blocks_bf16_fp8_perm_kernel, dim3(n_blocks), block, 0, s,
+                                   dev_src, dev_dst, dev_scales, a);
+            else
+                hipLaunchKernelGGL(dequant_blocks_fp8_bf16_perm_kernel, dim3(grid), block, 0, s,
+                                   dev_src, dev_dst, dev_scales, a);
+            break;
+        case PageCodec::kMxfp4:
+            if (store)
+                hipLaunchKernelGGL(quant_blocks_bf16_mxfp4_perm_kernel, dim3(grid), block, 0, s,
+                                   dev_src, dev_dst, a);
+            else
+                hipLaunchKernelGGL(dequant_blocks_mxfp4_bf16_perm_kernel, dim3(grid), block, 0,
+                                   s, dev_src, dev_dst, a);
+            break;
+        default:
+            return false;
+    }
+    HIP_OK(hipGetLastError());
+    return true;
+}
+
 // --- fingerprint -----------------------------------------------------------
 // Position-salted 64-bit mix (splitmix64 finalizer); XOR-combined across a
 // block so the reduction is order-free, deterministic, and parallel.

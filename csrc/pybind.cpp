@@ -445,6 +445,83 @@ bool load_sliced_py(int codec_id, const std::vector<uint64_t>& stored,
     return ok;
 }
 
+// ---- permuted pages (docs/design.md, "permuted pages") -----------------------
+// A permutation from Python: None, or (outer, rows, cols, piece) with the
+// piece in units of `unit` bytes (the tensor's element size; 1 for the
+// byte-level debug entries).
+PagePermute perm_from_py(const char* what, const py::object& o, uint64_t unit) {
+    PagePermute pm;
+    if (o.is_none()) return pm;
+    py::tuple t = o.cast<py::tuple>();
+    if (t.size() != 4)
+        throw std::invalid_argument(std::string(what) +
+                                    ": a permutation is (outer, rows, cols, piece)");
+    pm.outer = t[0].cast<uint32_t>();
+    pm.rows = t[1].cast<uint32_t>();
+    pm.cols = t[2].cast<uint32_t>();
+    pm.piece_bytes = t[3].cast<uint64_t>() * unit;
+    return pm;
+}
+
+// The two permute launchers, called directly: one client page pointer and one
+// pool pointer per block. Both return what the launcher returns, so a refusal
+// is False, not an exception; aligned16 is computed from the pointers as
+// Shard::submit_copy does. force_byte passes aligned16 = false, which selects
+// the byte kernel for aligned operands too.
+bool copy_blocks_perm_py(const std::vector<uint64_t>& client, const std::vector<uint64_t>& pool,
+                         size_t bytes_per_block, const py::object& perm, uint32_t n_segments,
+                         uint64_t segment_stride, bool to_pool, int device, bool force_byte) {
+    const char* what = "_dbg_copy_blocks_perm";
+    const PagePermute pm = perm_from_py(what, perm, 1);
+    require_gpu_and_pairs(what, client, pool);
+    size_t n = client.size();
+    py::gil_scoped_release rel;
+    Pinned<uint64_t> h_client(n ? n : 1), h_pool(n ? n : 1);
+    memcpy(h_client.p, client.data(), n * 8);
+    memcpy(h_pool.p, pool.data(), n * 8);
+    ScopedStream st(device);
+    bool ok = gpu::launch_copy_blocks_perm(
+        device, st.s, to_pool ? h_client.p : h_pool.p, to_pool ? h_pool.p : h_client.p,
+        static_cast<int>(n), bytes_per_block, !force_byte && all_aligned16(client, pool),
+        PageSegments{n_segments, segment_stride}, to_pool ? PageDir::kStore : PageDir::kLoad, pm);
+    // Always drain the stream before the pinned descriptors go away.
+    if (!gpu::stream_sync(st.s))
+        throw std::runtime_error(std::string(what) + " failed: " + gpu::last_error());
+    return ok;
+}
+
+// to_pool quantizes (the scales come back), else dequantizes (they go in).
+std::pair<bool, std::vector<float>> transform_blocks_perm_py(
+    int codec_id, bool to_pool, const std::vector<uint64_t>& client,
+    const std::vector<uint64_t>& pool, std::vector<float> scales, size_t elems_per_block,
+    const py::object& perm, uint32_t n_segments, uint64_t segment_stride, int device) {
+    const char* what = "_dbg_transform_blocks_perm";
+    const PageCodec codec = codec_from_id(what, codec_id);
+    const PagePermute pm = perm_from_py(what, perm, 1);
+    require_gpu_and_pairs(what, client, pool);
+    size_t n = client.size();
+    const bool page_scale = page_codec_info(codec).page_scale;
+    if (page_scale && !to_pool && scales.size() != n)
+        throw std::invalid_argument(std::string(what) + ": one scale per block");
+    scales.resize(page_scale ? n : 0);
+    py::gil_scoped_release rel;
+    Pinned<uint64_t> h_client(n ? n : 1), h_pool(n ? n : 1);
+    Pinned<float> h_scale(n ? n : 1);
+    memcpy(h_client.p, client.data(), n * 8);
+    memcpy(h_pool.p, pool.data(), n * 8);
+    memcpy(h_scale.p, scales.data(), scales.size() * sizeof(float));
+    ScopedStream st(device);
+    bool ok = gpu::launch_transform_blocks_perm(
+        device, st.s, codec, to_pool ? PageDir::kStore : PageDir::kLoad,
+        to_pool ? h_client.p : h_pool.p, to_pool ? h_pool.p : h_client.p, h_scale.p,
+        static_cast<int>(n), elems_per_block, all_aligned16(client, pool),
+        PageSegments{n_segments, segment_stride}, pm);
+    if (!gpu::stream_sync(st.s))
+        throw std::runtime_error(std::string(what) + " failed: " + gpu::last_error());
+    if (ok) memcpy(scales.data(), h_scale.p, scales.size() * sizeof(float));
+    return {ok, scales};
+}
+
 // (codec id, stored bytes) of a request with these flags and this logical
 // page size, by the codec table alone (host-only).
 std::pair<int, size_t> page_codec_py(uint32_t flags, size_t page_bytes) {
@@ -520,7 +597,13 @@ struct ShardRun {
 py::tuple shard_run_impl(const char* what, int device, int n_streams, int slots_per_stream,
                          size_t max_descs_per_slot, const py::list& copy_jobs,
                          const py::list& fabric_jobs, int n_threads, double timeout_s,
-                         const py::list* slices, const py::list* tsets = nullptr) {
+                         const py::list* slices, const py::list* tsets = nullptr,
+                         const py::list* perms = nullptr) {
+    // perms (null but for _dbg_shard_run_perm): one entry per copy job, None
+    // or the job's permutation in bytes as perm_from_py takes it.
+    if (perms && perms->size() != copy_jobs.size())
+        throw std::invalid_argument(std::string(what) +
+                                    ": one permutation (or None) per copy job");
     if (slices && slices->size() != copy_jobs.size())
         throw std::invalid_argument(std::string(what) + ": one slice (or None) per copy job");
     if (tsets && tsets->size() != copy_jobs.size())
@@ -556,6 +639,7 @@ py::tuple shard_run_impl(const char* what, int device, int n_streams, int slots_
             j.scales = std::make_shared<std::vector<float>>(t[7].cast<std::vector<float>>());
         j.scales_off = t[8].cast<size_t>();
         if (slices) j.slice = slice_from_py(what, (*slices)[i], 1);
+        if (perms) j.perm = perm_from_py(what, (*perms)[i], 1);
         if (tsets && !py::object((*tsets)[i]).is_none()) {
             py::tuple ts = (*tsets)[i].cast<py::tuple>();
             if (ts.size() != 2)
@@ -792,11 +876,15 @@ PYBIND11_MODULE(_native, m) {
             [](ClientConn& c, const std::string& op, py::list keys, py::buffer offsets,
                uint64_t element_size, int block_size, uintptr_t ptr, int device,
                bool sync_response, uint32_t extra_flags, uint32_t n_segments,
-               uint64_t segment_stride, const py::object& page_slice) {
+               uint64_t segment_stride, const py::object& page_slice,
+               const py::object& page_permute) {
                 // page_slice: None or (n_pieces, page, offset, piece, stride)
                 // in elements; reads only (the client refuses it on 'W').
                 const PackedLocalSliceExt sl =
                     slice_to_wire(slice_from_py("rw_local", page_slice, element_size));
+                // page_permute: None or (outer, rows, cols, piece) in elements
+                const PackedLocalPermExt pe =
+                    permute_to_wire(perm_from_py("rw_local", page_permute, element_size));
                 // Build the NUL-joined key blob and byte offsets in C++ —
                 // no Python-side join/numpy work on the hot path.
                 py::buffer_info ob = offsets.request();
@@ -820,23 +908,27 @@ PYBIND11_MODULE(_native, m) {
                 return c.rw_local_packed(op.empty() ? 'W' : op[0], blob.data(), blob.size(),
                                          byte_offs.data(), n, block_size, ptr, device,
                                          sync_response, nullptr, extra_flags, n_segments,
-                                         segment_stride * element_size, &sl);
+                                         segment_stride * element_size, &sl, nullptr, &pe);
             },
             py::arg("op"), py::arg("keys"), py::arg("offsets"), py::arg("element_size"),
             py::arg("block_size"), py::arg("ptr"), py::arg("device"),
             py::arg("sync_response") = false, py::arg("extra_flags") = 0,
             py::arg("n_segments") = 1, py::arg("segment_stride") = 0,
-            py::arg("page_slice") = py::none())
+            py::arg("page_slice") = py::none(), py::arg("page_permute") = py::none())
         .def(
             "rw_local_blob",
             [](ClientConn& c, const std::string& op, py::buffer blob, py::buffer offsets,
                uint64_t element_size, int block_size, uintptr_t ptr, int device,
                bool sync_response, uint32_t extra_flags, uint32_t n_segments,
-               uint64_t segment_stride, const py::object& page_slice) {
+               uint64_t segment_stride, const py::object& page_slice,
+               const py::object& page_permute) {
                 // page_slice: None or (n_pieces, page, offset, piece, stride)
                 // in elements; reads only (the client refuses it on 'W').
                 const PackedLocalSliceExt sl =
                     slice_to_wire(slice_from_py("rw_local", page_slice, element_size));
+                // page_permute: None or (outer, rows, cols, piece) in elements
+                const PackedLocalPermExt pe =
+                    permute_to_wire(perm_from_py("rw_local", page_permute, element_size));
                 // Zero-pack fast path: keys as one NUL-separated bytes blob
                 // (engines cache the serialized page-key chain; re-joining
                 // 2k Python strings costs ~30 µs per request otherwise).
@@ -853,20 +945,23 @@ PYBIND11_MODULE(_native, m) {
                 return c.rw_local_packed(op.empty() ? 'W' : op[0], bp, blen, byte_offs.data(),
                                          n, block_size, ptr, device, sync_response, nullptr,
                                          extra_flags, n_segments,
-                                         segment_stride * element_size, &sl);
+                                         segment_stride * element_size, &sl, nullptr, &pe);
             },
             py::arg("op"), py::arg("blob"), py::arg("offsets"), py::arg("element_size"),
             py::arg("block_size"), py::arg("ptr"), py::arg("device"),
             py::arg("sync_response") = false, py::arg("extra_flags") = 0,
             py::arg("n_segments") = 1, py::arg("segment_stride") = 0,
-            py::arg("page_slice") = py::none())
+            py::arg("page_slice") = py::none(), py::arg("page_permute") = py::none())
         .def(
             "rw_local_blob_async",
             [](ClientConn& c, const std::string& op, py::buffer blob, py::buffer offsets,
                uint64_t element_size, int block_size, uintptr_t ptr, int device,
-               uint32_t n_segments, uint64_t segment_stride, const py::object& page_slice) {
+               uint32_t n_segments, uint64_t segment_stride, const py::object& page_slice,
+               const py::object& page_permute) {
                 const PackedLocalSliceExt sl =
                     slice_to_wire(slice_from_py("rw_local", page_slice, element_size));
+                const PackedLocalPermExt pe =
+                    permute_to_wire(perm_from_py("rw_local", page_permute, element_size));
                 // Ticketed form: push the (sync-response) op and return a
                 // ticket to pass to wait_local_ticket — the engine overlaps
                 // its own work with the copy. Ticket 0 = already complete
@@ -887,14 +982,15 @@ PYBIND11_MODULE(_native, m) {
                     ret = c.rw_local_packed(op.empty() ? 'R' : op[0], bp, blen,
                                             byte_offs.data(), n, block_size, ptr, device,
                                             /*sync_response=*/true, &ticket, 0, n_segments,
-                                            segment_stride * element_size, &sl);
+                                            segment_stride * element_size, &sl, nullptr,
+                                            &pe);
                 }
                 return py::make_tuple(ret, ticket);
             },
             py::arg("op"), py::arg("blob"), py::arg("offsets"), py::arg("element_size"),
             py::arg("block_size"), py::arg("ptr"), py::arg("device"),
             py::arg("n_segments") = 1, py::arg("segment_stride") = 0,
-            py::arg("page_slice") = py::none())
+            py::arg("page_slice") = py::none(), py::arg("page_permute") = py::none())
         .def(
             "rw_tset_blob",
             [](ClientConn& c, const std::string& op, py::buffer blob, py::buffer offsets,
@@ -1208,6 +1304,50 @@ PYBIND11_MODULE(_native, m) {
           py::arg("device"), py::arg("n_streams"), py::arg("slots_per_stream"),
           py::arg("max_descs_per_slot"), py::arg("copy_jobs"), py::arg("tsets"),
           py::arg("n_threads"), py::arg("timeout_s"), py::arg("slices") = py::none());
+    // The permute-geometry predicate; the permutation is (outer, rows, cols,
+    // piece_bytes), the client segments as above.
+    m.def("_dbg_permute_legal",
+          [](int codec, size_t page_bytes, const py::object& perm, uint32_t n_segments,
+             uint64_t stride_bytes) {
+              if (perm.is_none())
+                  throw std::invalid_argument("_dbg_permute_legal: a permutation is a tuple of 4");
+              return permute_legal(codec_from_id("_dbg_permute_legal", codec), page_bytes,
+                                   perm_from_py("_dbg_permute_legal", perm, 1),
+                                   PageSegments{n_segments, stride_bytes});
+          },
+          py::arg("codec"), py::arg("page_bytes"), py::arg("perm"), py::arg("n_segments") = 1,
+          py::arg("stride_bytes") = 0);
+    m.attr("_MAX_PERM_PIECES") = kMaxPermPieces;
+    m.attr("_PERM_THREADS") = gpu::kPermThreads;
+    // The permute launchers (gpu.h), called directly: one client page pointer
+    // and one pool pointer per block, the permutation in bytes. Return False
+    // for what the launcher refuses; the transform form returns (ok, scales).
+    m.def("_dbg_copy_blocks_perm", &copy_blocks_perm_py, py::arg("client_ptrs"),
+          py::arg("pool_ptrs"), py::arg("bytes_per_block"), py::arg("perm"),
+          py::arg("n_segments") = 1, py::arg("segment_stride") = 0, py::arg("to_pool") = true,
+          py::arg("device") = 0, py::arg("force_byte") = false);
+    m.def("_dbg_transform_blocks_perm", &transform_blocks_perm_py, py::arg("codec"),
+          py::arg("to_pool"), py::arg("client_ptrs"), py::arg("pool_ptrs"), py::arg("scales"),
+          py::arg("elems_per_block"), py::arg("perm"), py::arg("n_segments") = 1,
+          py::arg("segment_stride") = 0, py::arg("device") = 0);
+    // _dbg_shard_run's copy jobs, each with a permutation (or None) from
+    // `perms`; `slices` as for _dbg_shard_run_sliced (both on one job is
+    // refused).
+    m.def("_dbg_shard_run_perm",
+          [](int device, int n_streams, int slots_per_stream, size_t max_descs_per_slot,
+             const py::list& copy_jobs, const py::list& perms, int n_threads, double timeout_s,
+             const py::object& slices) -> py::object {
+              py::list sl;
+              if (!slices.is_none()) sl = slices.cast<py::list>();
+              py::tuple out = shard_run_impl("_dbg_shard_run_perm", device, n_streams,
+                                             slots_per_stream, max_descs_per_slot, copy_jobs,
+                                             py::list(), n_threads, timeout_s,
+                                             slices.is_none() ? nullptr : &sl, nullptr, &perms);
+              return out[0];
+          },
+          py::arg("device"), py::arg("n_streams"), py::arg("slots_per_stream"),
+          py::arg("max_descs_per_slot"), py::arg("copy_jobs"), py::arg("perms"),
+          py::arg("n_threads"), py::arg("timeout_s"), py::arg("slices") = py::none());
     // Jobs through a real Shard at small limits. A copy job is (src_ptrs,
     // dst_ptrs, bytes_per_block, codec_id, store, n_segments, segment_stride,
     // scales or None, scales_off), a fabric job (is_put, host buffer,
@@ -1229,9 +1369,21 @@ PYBIND11_MODULE(_native, m) {
              uint32_t flags, uint32_t alloc_mb, py::bytes ipc,
              const std::vector<uint64_t>& offsets, const std::vector<std::string>& keys,
              uint32_t n_segments, uint64_t segment_stride, const py::object& slice,
-             const py::object& tensor_set) {
+             const py::object& tensor_set, const py::object& permute) {
               const PackedLocalSliceExt sl =
                   slice_to_wire(slice_from_py("_dbg_build_packed_local", slice, 1));
+              // None, or (outer, rows, cols, piece_bytes[, rsvd])
+              PackedLocalPermExt pe{};
+              if (!permute.is_none()) {
+                  py::tuple t = permute.cast<py::tuple>();
+                  if (t.size() != 4 && t.size() != 5)
+                      throw std::invalid_argument("_dbg_build_packed_local: a permutation is "
+                                                  "(outer, rows, cols, piece_bytes)");
+                  pe = PackedLocalPermExt{t[0].cast<uint32_t>(), t[1].cast<uint32_t>(),
+                                          t[2].cast<uint32_t>(),
+                                          t.size() == 5 ? t[4].cast<uint32_t>() : 0,
+                                          t[3].cast<uint64_t>()};
+              }
               // None, or (set_id, n_tensors[, rsvd])
               PackedLocalTensorExt ts{};
               if (!tensor_set.is_none()) {
@@ -1265,14 +1417,14 @@ PYBIND11_MODULE(_native, m) {
               }
               auto v = build_packed_local(h, n_segments, segment_stride, offsets.data(),
                                           blob.data(), blob.size(), &sl,
-                                          tensor_set.is_none() ? nullptr : &ts);
+                                          tensor_set.is_none() ? nullptr : &ts, &pe);
               return py::bytes(reinterpret_cast<const char*>(v.data()), v.size());
           },
           py::arg("device"), py::arg("pid"), py::arg("base_ptr"), py::arg("base_offset"),
           py::arg("block_size"), py::arg("flags"), py::arg("alloc_mb"), py::arg("ipc"),
           py::arg("offsets"), py::arg("keys"), py::arg("n_segments") = 1,
           py::arg("segment_stride") = 0, py::arg("slice") = py::none(),
-          py::arg("tensor_set") = py::none());
+          py::arg("tensor_set") = py::none(), py::arg("permute") = py::none());
     m.def("_dbg_parse_packed_local", [](const std::string& op, py::bytes data) {
         std::string s = data;
         PackedLocalReq r;
@@ -1301,6 +1453,12 @@ PYBIND11_MODULE(_native, m) {
             d["tensor_set"] = py::make_tuple(r.tset.set_id, r.tset.n_tensors);
         else
             d["tensor_set"] = py::none();
+        // None, or (outer, rows, cols, piece_bytes)
+        if (r.perm.rows)
+            d["permute"] = py::make_tuple(r.perm.outer, r.perm.rows, r.perm.cols,
+                                          r.perm.piece_bytes);
+        else
+            d["permute"] = py::none();
         py::list offs, keys;
         for (auto& [key, off] : r.blocks) {
             offs.append(off);

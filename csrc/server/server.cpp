@@ -544,6 +544,7 @@ bool parse_packed_local(char op, const uint8_t* body, size_t body_len, Server::L
     v->has_tset = req.has_tset;
     v->tset_id = req.tset.set_id;
     v->tset_n = req.tset.n_tensors;
+    v->perm = permute_from_wire(req.perm);
     v->ipc = body + offsetof(PackedLocalHdr, ipc);
     v->ipc_len = 64;
     v->blocks = std::move(req.blocks);
@@ -826,6 +827,12 @@ void Server::op_local_write(Conn* c, const LocalView& msg, const ReqCtx& ctx) {
     } else if (!segments_legal(codec, page, msg.n_segments, msg.segment_stride)) {
         return reply_local(c, ctx, INVALID_REQ);
     }
+    // Permuted source pages: the geometry must tile THIS page size, with
+    // pieces the codec's kernels can move.
+    const bool permuted = permute_is_set(msg.perm);
+    if (permuted && (tset || !permute_legal(codec, page, msg.perm,
+                                            PageSegments{msg.n_segments, msg.segment_stride})))
+        return reply_local(c, ctx, INVALID_REQ);
     // The quantize kernels load 16 bytes per lane: every source page must
     // start 16-byte aligned (pool blocks always do), and a 16-byte stride
     // then keeps every segment aligned.
@@ -909,6 +916,7 @@ void Server::op_local_write(Conn* c, const LocalView& msg, const ReqCtx& ctx) {
         job.tensor_bases = tset->bases;
         job.segs_per_tensor = msg.n_segments / static_cast<uint32_t>(tset->bases->size());
     }
+    job.perm = msg.perm;
     job.scales = scales_out;
     for (size_t i = 0; i < n_fresh; i++) {
         auto* e = slab_batch.make();
@@ -1061,6 +1069,11 @@ void Server::op_local_read(Conn* c, const LocalView& msg, const ReqCtx& ctx) {
     if (sliced && (!slice_legal(PageCodec::kNone, msg.slice, client_seg) ||
                    page != msg.slice.n * msg.slice.piece_bytes))
         return reply_local(c, ctx, INVALID_REQ);
+    // Permuted read: plain rules here as well, every entry against its own
+    // codec in the sweep.
+    const bool permuted = permute_is_set(msg.perm);
+    if (permuted && (sliced || tset || !permute_legal(PageCodec::kNone, page, msg.perm, client_seg)))
+        return reply_local(c, ctx, INVALID_REQ);
 
     auto tr0 = Clock::now();
     // Group blocks by the shard whose GPU EXECUTES the copy. For same-GPU
@@ -1120,6 +1133,17 @@ void Server::op_local_read(Conn* c, const LocalView& msg, const ReqCtx& ctx) {
                     err = INVALID_REQ;
                     return false;
                 }
+            } else if (permuted) {
+                // As for a slice: the page must be the written size for every
+                // codec (the permutation is of the WHOLE page), the geometry
+                // legal for the entry's codec, and a compressed entry needs
+                // the 16-byte-aligned client address.
+                if (!stored_matches(e->codec, e->size, page) ||
+                    !permute_legal(e->codec, page, msg.perm, client_seg) ||
+                    (page_codec_transforms(e->codec) && (client_addr + b.second) % 16 != 0)) {
+                    err = INVALID_REQ;
+                    return false;
+                }
             } else if (tset) {
                 // The whole request against the entry's codec (geometry,
                 // aligned bases and offsets), once per codec; the page must
@@ -1159,6 +1183,7 @@ void Server::op_local_read(Conn* c, const LocalView& msg, const ReqCtx& ctx) {
                     it->second.n_segments = msg.n_segments;
                     it->second.segment_stride = msg.segment_stride;
                     it->second.slice = msg.slice;
+                    it->second.perm = msg.perm;
                     if (tset) {
                         it->second.tensor_bases = tset->bases;
                         it->second.segs_per_tensor =

@@ -155,6 +155,10 @@ class Server {
         bool has_tset = false;
         uint32_t tset_id = 0;
         uint32_t tset_n = 0;
+        // Permuted pages (packed ops only): perm.rows != 0 says that the
+        // client holds every page's pieces with two axes exchanged. Never
+        // together with a slice or a tensor set.
+        PagePermute perm;
         const uint8_t* ipc = nullptr;
         size_t ipc_len = 0;
         std::vector<std::pair<std::string_view, uint64_t>> blocks;

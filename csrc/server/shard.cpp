@@ -242,6 +242,12 @@ bool Shard::submit_copy(CopyJob&& job) {
     if (sliced && (job.dir != PageDir::kLoad || !slice_legal(job.codec, job.slice, seg) ||
                    job.bytes_per_block != job.slice.n * job.slice.piece_bytes))
         return false;
+    // A permutation is a client-side geometry of its own: not next to a
+    // slice or a tensor set.
+    const bool permuted = permute_is_set(job.perm);
+    if (permuted && (sliced || tset ||
+                     !permute_legal(job.codec, job.bytes_per_block, job.perm, seg)))
+        return false;
     // A codec with a per-page scale needs one scale slot per block.
     const bool page_scale = page_codec_info(job.codec).page_scale;
     if (page_scale && (!job.scales || job.scales->size() < job.scales_off + n)) return false;
@@ -266,6 +272,7 @@ bool Shard::submit_copy(CopyJob&& job) {
             sub.slice = job.slice;
             sub.tensor_bases = job.tensor_bases;
             sub.segs_per_tensor = job.segs_per_tensor;
+            sub.perm = job.perm;
             sub.scales = job.scales;
             sub.scales_off = job.scales_off + off;
             sub.src.assign(job.src.begin() + static_cast<long>(off),
@@ -321,6 +328,30 @@ bool Shard::submit_copy(CopyJob&& job) {
             if (job.done) job.done(true);
             return true;
         }
+        if (permuted) {
+            // Piece (o, r, c): stored at its canonical index, in the client
+            // page at the exchanged one, that page being split into segments.
+            const PagePermute& pm = job.perm;
+            const bool store = job.dir == PageDir::kStore;
+            const uint64_t per_seg = static_cast<uint64_t>(pm.outer) * pm.rows * pm.cols / seg.n;
+            for (size_t i = 0; i < n; i++)
+                for (uint64_t o = 0; o < pm.outer; o++)
+                    for (uint64_t r = 0; r < pm.rows; r++)
+                        for (uint64_t c = 0; c < pm.cols; c++) {
+                            const uint64_t q = (o * pm.rows + r) * pm.cols + c;
+                            const uint64_t p = (o * pm.cols + c) * pm.rows + r;
+                            const uint64_t client = (store ? job.src[i] : job.dst[i]) +
+                                                    (p / per_seg) * seg.stride_bytes +
+                                                    (p % per_seg) * pm.piece_bytes;
+                            const uint64_t pool =
+                                (store ? job.dst[i] : job.src[i]) + q * pm.piece_bytes;
+                            memcpy(reinterpret_cast<void*>(store ? pool : client),
+                                   reinterpret_cast<const void*>(store ? client : pool),
+                                   pm.piece_bytes);
+                        }
+            if (job.done) job.done(true);
+            return true;
+        }
         const size_t seg_bytes = job.bytes_per_block / seg.n;
         const uint64_t src_step = job.dir == PageDir::kStore ? seg.stride_bytes : seg_bytes;
         const uint64_t dst_step = job.dir == PageDir::kStore ? seg_bytes : seg.stride_bytes;
@@ -347,6 +378,8 @@ bool Shard::submit_copy(CopyJob&& job) {
     if (sliced)
         aligned = aligned && job.slice.offset % 16 == 0 && job.slice.piece_bytes % 16 == 0 &&
                   (job.slice.n == 1 || job.slice.stride % 16 == 0);
+    // A permuted page's pieces start at multiples of the piece on both sides.
+    if (permuted) aligned = aligned && job.perm.piece_bytes % 16 == 0;
     if (aligned) {
         for (size_t i = 0; i < n && aligned; i++)
             aligned = (job.src[i] % 16 == 0) && (job.dst[i] % 16 == 0);
@@ -389,7 +422,7 @@ bool Shard::submit_copy(CopyJob&& job) {
     // Small aligned batches: descriptors ride in the kernel arguments.
     // (Segmented, sliced and tensor-set jobs always use the pinned-descriptor
     // kernels.)
-    if (aligned && n <= 16 && !transforms && !segmented && !sliced && !tset) {
+    if (aligned && n <= 16 && !transforms && !segmented && !sliced && !tset && !permuted) {
         Slot* slot = acquire_slot(sc);
         if (!slot) return false;
         bool ok = gpu::set_device(opt_.device) &&
@@ -452,6 +485,21 @@ bool Shard::submit_copy(CopyJob&& job) {
                                opt_.device, sc.stream, job.codec, job.dir, dsrc, ddst,
                                slot->h_scale, static_cast<int>(take),
                                job.bytes_per_block / kPageElemBytes, aligned, seg, table);
+            }
+        } else if (permuted) {
+            if (!transforms) {
+                ok = ok && gpu::launch_copy_blocks_perm(opt_.device, sc.stream, dsrc, ddst,
+                                                        static_cast<int>(take),
+                                                        job.bytes_per_block, aligned, seg,
+                                                        job.dir, job.perm);
+            } else {
+                if (page_scale && job.dir == PageDir::kLoad)
+                    memcpy(slot->h_scale, job.scales->data() + job.scales_off + off,
+                           take * sizeof(float));
+                ok = ok && gpu::launch_transform_blocks_perm(
+                               opt_.device, sc.stream, job.codec, job.dir, dsrc, ddst,
+                               slot->h_scale, static_cast<int>(take),
+                               job.bytes_per_block / kPageElemBytes, aligned, seg, job.perm);
             }
         } else if (!transforms) {
             ok = ok && gpu::launch_copy_blocks(opt_.device, sc.stream, dsrc, ddst,

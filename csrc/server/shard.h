@@ -73,6 +73,12 @@ class Shard {
         // job never takes the inline-argument path and carries no slice.
         std::shared_ptr<const std::vector<uint64_t>> tensor_bases;
         uint32_t segs_per_tensor = 0;
+        // Permuted pages (core/page_codec.h, permute_legal): with perm.rows
+        // != 0 the CLIENT side holds every page's pieces with two axes
+        // exchanged, and segments apply to that client page. Both directions.
+        // Such a job never takes the inline-argument path and carries
+        // neither a slice nor a tensor set.
+        PagePermute perm;
         // Codecs with a per-page scale: block i's scale is
         // (*scales)[scales_off + i], written before done() by kStore and
         // read at submit by kLoad. Fan-out sub-jobs share the vector.

@@ -8,6 +8,7 @@ extensions (fingerprint_blocks, get_server_stats, unregister_server).
 from .lib import (
     InfinityConnection,
     PageSlice,
+    PagePermute,
     TensorSet,
     DisableTorchCaching,
     ClientConfig,
@@ -33,6 +34,7 @@ from .lib import (
 __all__ = [
     "InfinityConnection",
     "PageSlice",
+    "PagePermute",
     "TensorSet",
     "DisableTorchCaching",
     "register_server",

@@ -71,6 +71,16 @@ def parse_args():
                    help="with --slice: what a reader does without sliced reads, "
                         "for comparison: read whole pages into a bounce buffer, "
                         "then slice-copy the heads into place with torch")
+    p.add_argument("--hnd", type=int, default=0, metavar="H",
+                   help="permuted pages (local-GPU path): the buffers hold every "
+                        "page head-major, [2, H, T, --hnd-head], and the store "
+                        "keeps it token-major; T follows from the page size")
+    p.add_argument("--hnd-head", type=int, default=128,
+                   help="elements of one head of one token for --hnd")
+    p.add_argument("--hnd-baseline", action="store_true",
+                   help="with --hnd: what a reader does without permuted pages, "
+                        "read whole token-major pages, then permute().contiguous() "
+                        "each buffer with torch (inside the timed read)")
     p.add_argument("--verify", action="store_true")
     p.add_argument("--json", action="store_true", help="print a JSON summary")
     p.add_argument("--spawn-server", action="store_true",
@@ -78,6 +88,16 @@ def parse_args():
     p.add_argument("--prealloc-size", type=int, default=8,
                    help="pool GB per shard for --spawn-server")
     return p.parse_args()
+
+
+def hnd_geometry(args, page_elems):
+    """lib.PagePermute(2, T, H) of --hnd, or None."""
+    if not args.hnd:
+        return None
+    per_token = 2 * args.hnd * args.hnd_head
+    if args.hnd < 1 or args.hnd_head < 1 or page_elems % per_token != 0:
+        raise SystemExit("--hnd needs a page of 2 x T x H x --hnd-head elements")
+    return lib.PagePermute(2, page_elems // per_token, args.hnd)
 
 
 def slice_geometry(args):
@@ -266,10 +286,20 @@ def run_once(args, conn, local, device, bufs=None):
     def sub_of(i):  # block index -> (tensor index, element offset within it)
         return i // blocks_per_sub, (i % blocks_per_sub) * seg_elems
 
-    def geom(t):  # segment arguments for sub-tensor t: [N, n_pages, page/N]
-        if nseg == 1:
-            return {}
-        return {"segments": nseg, "segment_stride": t.numel() // nseg}
+    # --hnd: every page is [2, H, T, head] in the buffers.
+    perm = hnd_geometry(args, page_elems) if local else None
+    hnd_outs = None
+    if perm and args.hnd_baseline:  # allocated outside the timed window
+        hnd_outs = [torch.zeros_like(d) for d in dsts]
+        torch.cuda.synchronize()
+
+    def geom(t, permuted=True):  # geometry arguments for sub-tensor t
+        g = {}
+        if nseg != 1:  # [N, n_pages, page/N]
+            g.update(segments=nseg, segment_stride=t.numel() // nseg)
+        if perm and permuted:
+            g["page_permute"] = perm
+        return g
 
     # ---- write (layer-by-layer batches, like prefill; each step's slice
     # lives in ONE sub-tensor by construction) ----
@@ -279,7 +309,7 @@ def run_once(args, conn, local, device, bufs=None):
         t_idx, _ = sub_of(s0)
         pairs = [(keys[i], sub_of(i)[1]) for i in range(s0, hi)]
         if local:
-            if args.quant or nseg > 1:
+            if args.quant or nseg > 1 or perm:
                 conn.write_pages(srcs[t_idx], [p[0] for p in pairs],
                                  [p[1] for p in pairs], page_elems,
                                  quant=args.quant, **geom(srcs[t_idx]))
@@ -318,11 +348,18 @@ def run_once(args, conn, local, device, bufs=None):
                                                          sliced_elems,
                                                          page_slice=page_slice))
                     continue
-                tickets.append(conn.read_pages_async(dsts[t_idx], ks, offs,
-                                                     page_elems,
-                                                     **geom(dsts[t_idx])))
+                tickets.append(conn.read_pages_async(
+                    dsts[t_idx], ks, offs, page_elems,
+                    **geom(dsts[t_idx], permuted=not args.hnd_baseline)))
         for tk in tickets:
             conn.wait_read(tk)
+        if perm and args.hnd_baseline:
+            # the second pass a reader needs today: token-major pages landed
+            # in the bounce buffers (dsts), the engine wants them head-major
+            for d, o in zip(dsts, hnd_outs):
+                o.view(-1, 2, perm.cols, perm.rows, args.hnd_head).copy_(
+                    d.view(-1, 2, perm.rows, perm.cols, args.hnd_head).permute(0, 1, 3, 2, 4))
+            torch.cuda.synchronize()
         if sg and args.slice_baseline:
             # the second pass a reader needs today: pick the heads out of the
             # bounce buffer (dsts) into place
@@ -348,7 +385,7 @@ def run_once(args, conn, local, device, bufs=None):
             want = a.view(-1, rows, n_heads, head)[:, :, h0:h1].reshape(-1)
             assert _close(want.cpu(), o.cpu(), args.quant), "verification failed (slice)"
     elif args.verify:
-        for a, b in zip(srcs, dsts):
+        for a, b in zip(srcs, hnd_outs or dsts):
             assert _close(a.cpu(), b.cpu(), args.quant), "verification failed"
         if nseg > 1:
             _verify_contiguous_read(args, conn, srcs[0], dsts[0].device, keys, page_elems)
@@ -523,6 +560,12 @@ def main():
         if args.segments != 1 or args.slice:
             raise SystemExit("--fused-layers moves whole contiguous per-layer parts: "
                              "no --segments, no --slice")
+    if args.hnd_baseline and not args.hnd:
+        raise SystemExit("--hnd-baseline needs --hnd")
+    if args.hnd and (not args.local_gpu or args.segments != 1 or args.slice
+                     or args.fused_layers):
+        raise SystemExit("--hnd needs --local-gpu and no --segments, --slice or "
+                         "--fused-layers")
     if args.slice:
         if not args.local_gpu or args.segments != 1:
             raise SystemExit("--slice needs --local-gpu and --segments 1")

@@ -89,17 +89,21 @@ class PagedKVConnector:
     # -- prefill side ---------------------------------------------------------
     def save_layer(self, layer: int, kv: torch.Tensor, page_keys: List[str],
                    page_offsets, page_elems: int, segments: int = 1,
-                   segment_stride: int = 0):
+                   segment_stride: int = 0, page_permute=None):
         """Store this layer's pages of `kv` (offsets in elements). Call per
         layer as prefill produces them; uploads overlap later layers'
         compute (writes are async until sync()). segments / segment_stride:
         segmented pages, as in InfinityConnection.write_pages (local path
-        only, ValueError on the fabric path)."""
+        only, ValueError on the fabric path). page_permute: `kv` holds each
+        page with two piece axes exchanged (PagePermute; local path only)."""
         keys = [self._key(layer, k) for k in page_keys]
         if self.local:
             self.conn.write_pages(kv, keys, page_offsets, page_elems,
                                   quant=self.quant, segments=segments,
-                                  segment_stride=segment_stride)
+                                  segment_stride=segment_stride,
+                                  page_permute=page_permute)
+        elif page_permute is not None:
+            raise ValueError("permuted pages use the local GPU path")
         elif segments != 1:
             raise ValueError("segmented pages use the local GPU path")
         else:
@@ -114,13 +118,15 @@ class PagedKVConnector:
     # -- decode side ----------------------------------------------------------
     def load_layer(self, layer: int, kv_out: torch.Tensor, page_keys: List[str],
                    page_offsets, page_elems: int, segments: int = 1,
-                   segment_stride: int = 0, page_slice=None) -> bool:
+                   segment_stride: int = 0, page_slice=None, page_permute=None) -> bool:
         """Gather this layer's cached pages into the engine's KV tensor.
         Returns False if any page is missing (caller falls back to compute).
-        segments / segment_stride / page_slice: as in
+        segments / segment_stride / page_slice / page_permute: as in
         InfinityConnection.read_pages (page_elems is then the sliced page); a
         refused geometry raises ValueError."""
         keys = [self._key(layer, k) for k in page_keys]
+        # raises for an illegal geometry, the fabric path or a slice as well
+        self.conn._permute_arg(page_permute, page_elems, segments, None, page_slice)
         if segments != 1 and not self.local:
             raise ValueError("segmented pages use the local GPU path")
         if page_slice is not None and not self.local:
@@ -132,7 +138,8 @@ class PagedKVConnector:
                 self.conn.read_pages(kv_out, keys, page_offsets, page_elems,
                                      segments=segments,
                                      segment_stride=segment_stride,
-                                     page_slice=page_slice)
+                                     page_slice=page_slice,
+                                     page_permute=page_permute)
             else:
                 self._ensure_mr(kv_out)
                 blocks = [(k, int(o)) for k, o in zip(keys, page_offsets)]
@@ -145,12 +152,14 @@ class PagedKVConnector:
     def load_layer_async(self, layer: int, kv_out: torch.Tensor,
                          page_keys: List[str], page_offsets, page_elems: int,
                          segments: int = 1, segment_stride: int = 0,
-                         page_slice=None):
+                         page_slice=None, page_permute=None):
         """Ticketed prefetch (local path): push the gather and return a
         ticket; call wait_load(ticket) before touching kv_out. Lets decode
         overlap the next request's KV fetch with current compute. Returns
         None if any page was missing or the path is unavailable (caller
-        falls back to load_layer / recompute). page_slice as in load_layer."""
+        falls back to load_layer / recompute). page_slice and page_permute as
+        in load_layer."""
+        self.conn._permute_arg(page_permute, page_elems, segments, None, page_slice)
         if not self.local:
             if segments != 1:
                 raise ValueError("segmented pages use the local GPU path")
@@ -164,7 +173,8 @@ class PagedKVConnector:
             return self.conn.read_pages_async(kv_out, keys, page_offsets,
                                               page_elems, segments=segments,
                                               segment_stride=segment_stride,
-                                              page_slice=page_slice)
+                                              page_slice=page_slice,
+                                              page_permute=page_permute)
         except Exception:
             return None
 

@@ -274,6 +274,19 @@ class PageSlice(NamedTuple):
     count: int = 1
 
 
+class PagePermute(NamedTuple):
+    """Client-side piece order of a page (docs/design.md, "permuted pages"):
+    the tensor holds each page as [outer, cols, rows, piece] while the store
+    keeps, and every other reader sees, [outer, rows, cols, piece]. The piece
+    is page_size // (outer * rows * cols) elements. E.g. a head-major
+    [2, H, T, hd] cache block sharing keys with token-major [2, T, H, hd]
+    engines: PagePermute(2, T, H)."""
+
+    outer: int
+    rows: int
+    cols: int
+
+
 class TensorSet:
     """A registered tensor set (InfinityConnection.register_tensor_set): the
     server-side id and the tensors, which it keeps alive."""
@@ -466,6 +479,39 @@ class InfinityConnection:
             raise ValueError("a sliced page extends outside the tensor")
         # segments > 1: _check_segments bounds the segmented sliced page
 
+    # kMaxPermPieces in csrc/core/page_codec.h: the pieces one permuted page
+    # may have; tests/test_page_permute.py checks it against the native value.
+    MAX_PERM_PIECES = 1 << 20
+
+    def _permute_arg(self, page_permute, page_size: int, segments: int, quant=None,
+                     page_slice=None, tensor_set=None):
+        """Refuse (ValueError) a permuted request the store cannot serve,
+        before anything is sent: permute_legal's rules applied in elements.
+        Returns None, or what the native calls take: (outer, rows, cols,
+        piece) with the piece in elements."""
+        if page_permute is None:
+            return None
+        if page_slice is not None or tensor_set is not None:
+            raise ValueError("page_permute cannot be combined with page_slice or tensor_set")
+        if not self.local_connected:
+            raise ValueError("permuted pages use the local GPU path")
+        pm = PagePermute(*page_permute)
+        if min(pm) < 1:
+            raise ValueError("PagePermute outer, rows and cols must be >= 1")
+        pieces = pm.outer * pm.rows * pm.cols
+        if pieces > self.MAX_PERM_PIECES:
+            raise ValueError(f"a permuted page has at most {self.MAX_PERM_PIECES} pieces")
+        if page_size <= 0 or page_size % pieces != 0:
+            raise ValueError("page_size must be a positive multiple of outer * rows * cols")
+        if segments < 1 or pieces % segments != 0:
+            raise ValueError("outer * rows * cols must be a multiple of segments: a piece "
+                             "never straddles a segment")
+        piece = page_size // pieces
+        if quant is not None and piece % self.QUANT_MODES[quant][1] != 0:
+            raise ValueError(f"{quant} quant needs pieces of a multiple of "
+                             f"{self.QUANT_MODES[quant][1]} elements")
+        return (pm.outer, pm.rows, pm.cols, piece)
+
     @staticmethod
     def _slice_arg(page_slice):
         """The native (n_pieces, page, offset, piece, stride) tuple, or None."""
@@ -570,7 +616,8 @@ class InfinityConnection:
     def write_pages(self, cache: Optional[torch.Tensor], keys, offsets, page_size: int,
                     sync: bool = False, quant: Optional[str] = None,
                     segments: Optional[int] = None, segment_stride: int = 0,
-                    tensor_set=None, **unsupported):
+                    tensor_set=None, page_permute: Optional[PagePermute] = None,
+                    **unsupported):
         """sync=True completes the write in ONE round trip (the response is
         sent when the copy finishes); sync=False (default) returns after the
         server accepts, so uploads overlap compute — call sync() later.
@@ -612,6 +659,15 @@ class InfinityConnection:
         segment per tensor segment_stride is ignored). fp8 then keeps one
         scale over the parts of all tensors.
 
+        page_permute=PagePermute(outer, rows, cols): `cache` holds each page
+        as [outer, cols, rows, piece] (e.g. a head-major [2, H, T, hd] block)
+        and the stored page is the [outer, rows, cols, piece] one,
+        byte-identical to what a writer in that layout stores, so every
+        reader serves it. Works with every quant and with segments (which
+        apply to the page as `cache` holds it); local path only, not with
+        tensor_set; an illegal geometry is a ValueError before anything is
+        sent.
+
         Slices are read-only: write_pages has no page_slice parameter, and
         passing one is a ValueError."""
         if "page_slice" in unsupported:
@@ -620,6 +676,9 @@ class InfinityConnection:
             raise TypeError(f"write_pages() got an unexpected keyword argument "
                             f"{next(iter(unsupported))!r}")
         if tensor_set is not None:
+            if page_permute is not None:
+                raise ValueError("page_permute cannot be combined with page_slice or "
+                                 "tensor_set")
             if cache is not None:
                 raise ValueError("pass either cache or tensor_set")
             if quant is not None and quant not in self.QUANT_MODES:
@@ -638,6 +697,8 @@ class InfinityConnection:
         self._verify(cache)
         if segments != 1 and not self.local_connected:
             raise ValueError("segmented pages use the local GPU path")
+        if page_permute is not None and not self.local_connected:
+            raise ValueError("permuted pages use the local GPU path")
         assert self.local_connected, "write_pages uses the local GPU path"
         flags = 0
         if quant is not None:
@@ -658,17 +719,18 @@ class InfinityConnection:
                     "that are multiples of 8 elements")
         self._check_segments(cache.numel(), es, offs, page_size, segments,
                              segment_stride, quant)
+        perm = self._permute_arg(page_permute, page_size, segments, quant)
         if isinstance(keys, (bytes, bytearray, memoryview)):
             ret = self.conn.rw_local_blob(
                 self.OP_W, keys, offs, es, page_size * es,
                 cache.data_ptr(), _remap_device_id(cache), sync, flags,
-                segments, segment_stride,
+                segments, segment_stride, None, perm,
             )
         else:
             ret = self.conn.rw_local_keys(
                 self.OP_W, keys, offs, es, page_size * es,
                 cache.data_ptr(), _remap_device_id(cache), sync, flags,
-                segments, segment_stride,
+                segments, segment_stride, None, perm,
             )
         if ret < 0:
             raise Exception(f"Failed to write to infinistore, ret = {ret}")
@@ -676,7 +738,8 @@ class InfinityConnection:
 
     def read_pages(self, cache: Optional[torch.Tensor], keys, offsets, page_size: int,
                    segments: Optional[int] = None, segment_stride: int = 0,
-                   page_slice: Optional[PageSlice] = None, tensor_set=None):
+                   page_slice: Optional[PageSlice] = None, tensor_set=None,
+                   page_permute: Optional[PagePermute] = None):
         """segments / segment_stride: scatter each page into that many equal
         pieces of `cache` (see write_pages), however the page was written.
         Local path only.
@@ -694,8 +757,13 @@ class InfinityConnection:
 
         tensor_set=ts in place of `cache` (pass None): scatter each page over
         the tensors of the set (see write_pages), however it was written.
-        Not together with page_slice."""
+        Not together with page_slice.
+
+        page_permute: deliver each page as [outer, cols, rows, piece] (see
+        write_pages), however it was written. page_size must be the written
+        one. Not together with page_slice or tensor_set."""
         if tensor_set is not None:
+            self._permute_arg(page_permute, page_size, 1, None, page_slice, tensor_set)
             offs = self._tensor_set_read_args(cache, tensor_set, offsets, page_size,
                                               segments, segment_stride, page_slice)
             segments = len(tensor_set.tensors) if segments is None else segments
@@ -710,6 +778,7 @@ class InfinityConnection:
             raise ValueError("segmented pages use the local GPU path")
         if page_slice is not None and not self.local_connected:
             raise ValueError("sliced reads use the local GPU path")
+        perm = self._permute_arg(page_permute, page_size, segments, None, page_slice)
         es = cache.element_size()
         if self.local_connected:
             offs = np.asarray(offsets, dtype=np.uint64)
@@ -722,13 +791,13 @@ class InfinityConnection:
                 ret = self.conn.rw_local_blob(
                     self.OP_R, keys, offs, es, page_size * es,
                     cache.data_ptr(), _remap_device_id(cache), False, 0,
-                    segments, segment_stride, self._slice_arg(page_slice),
+                    segments, segment_stride, self._slice_arg(page_slice), perm,
                 )
             else:
                 ret = self.conn.rw_local_keys(
                     self.OP_R, keys, offs, es, page_size * es,
                     cache.data_ptr(), _remap_device_id(cache), False, 0,
-                    segments, segment_stride, self._slice_arg(page_slice),
+                    segments, segment_stride, self._slice_arg(page_slice), perm,
                 )
         elif self.rdma_connected:
             blocks = [(k, int(o) * es) for k, o in zip(keys, offsets)]
@@ -752,14 +821,17 @@ class InfinityConnection:
 
     def read_pages_async(self, cache: Optional[torch.Tensor], keys, offsets, page_size: int,
                          segments: Optional[int] = None, segment_stride: int = 0,
-                         page_slice: Optional[PageSlice] = None, tensor_set=None):
+                         page_slice: Optional[PageSlice] = None, tensor_set=None,
+                         page_permute: Optional[PagePermute] = None):
         """Ticketed read (local path, shm ring): pushes the request and
         returns a ticket; call wait_read(ticket) before using the data. Lets
         an engine overlap its own work (or further requests) with the copy —
         e.g. prefetching the next sequence's KV pages while decoding. Falls
         back to a blocking read (ticket 0) when the ring is unavailable.
-        segments / segment_stride / page_slice / tensor_set as in read_pages."""
+        segments / segment_stride / page_slice / tensor_set / page_permute as
+        in read_pages."""
         if tensor_set is not None:
+            self._permute_arg(page_permute, page_size, 1, None, page_slice, tensor_set)
             offs = self._tensor_set_read_args(cache, tensor_set, offsets, page_size,
                                               segments, segment_stride, page_slice)
             segments = len(tensor_set.tensors) if segments is None else segments
@@ -774,6 +846,7 @@ class InfinityConnection:
             raise ValueError("segmented pages use the local GPU path")
         if page_slice is not None and not self.local_connected:
             raise ValueError("sliced reads use the local GPU path")
+        perm = self._permute_arg(page_permute, page_size, segments, None, page_slice)
         assert self.local_connected, "read_pages_async uses the local GPU path"
         es = cache.element_size()
         offs = np.asarray(offsets, dtype=np.uint64)
@@ -787,7 +860,7 @@ class InfinityConnection:
         ret, ticket = self.conn.rw_local_blob_async(
             self.OP_R, keys, offs, es, page_size * es,
             cache.data_ptr(), _remap_device_id(cache), segments, segment_stride,
-            self._slice_arg(page_slice),
+            self._slice_arg(page_slice), perm,
         )
         if ret < 0:
             raise Exception(f"Failed to read from infinistore, ret = {ret}")

@@ -44,7 +44,7 @@ from typing import Dict, List, Optional, Sequence
 import torch
 
 from .kv_connector import PagedKVConnector, token_page_hashes
-from .lib import PageSlice
+from .lib import PagePermute, PageSlice
 
 
 class InfiniStoreKVAdapter:
@@ -93,9 +93,20 @@ class InfiniStoreKVAdapter:
             drops the layer index, so fused and per-layer pages of one model
             tag never collide, and neither kind of adapter sees the other's
             pages. With quant="fp8" the page's one scale spans all layers.
+        cache_layout, cache_kv_heads: "nhd" (default): a block's K (and V) is
+            token-major ``[block_tokens, n_kv, head]``, which is also what the
+            store keeps. "hnd": head-major ``[n_kv, block_tokens, head]`` with
+            ``n_kv = cache_kv_heads`` (required), as engines with
+            heterogeneous tensor parallelism allocate. Every page then
+            travels as a permuted page (docs/design.md, "permuted pages") and
+            is stored exactly as an "nhd" engine stores it, so engines of
+            either layout share keys. Works with both kv_layout values and
+            every quant; needs the local path; with head_range or
+            layer_pages="fused" it raises ValueError.
     """
 
     KV_LAYOUTS = ("block_major", "kv_major")
+    CACHE_LAYOUTS = ("nhd", "hnd")
     LAYER_PAGES = ("per_layer", "fused")
 
     def __init__(self, host: str, port: int, model_tag: str, n_layers: int,
@@ -103,9 +114,29 @@ class InfiniStoreKVAdapter:
                  quant: Optional[str] = None, kv_layout: str = "block_major",
                  stored_kv_heads: Optional[int] = None,
                  head_range: Optional[Sequence[int]] = None,
-                 head_dim: Optional[int] = None, layer_pages: str = "per_layer"):
+                 head_dim: Optional[int] = None, layer_pages: str = "per_layer",
+                 cache_layout: str = "nhd", cache_kv_heads: Optional[int] = None):
         if layer_pages not in self.LAYER_PAGES:
             raise ValueError(f"layer_pages must be one of {self.LAYER_PAGES}")
+        if cache_layout not in self.CACHE_LAYOUTS:
+            raise ValueError(f"cache_layout must be one of {self.CACHE_LAYOUTS}")
+        self._page_permute = None
+        if cache_layout == "hnd":
+            if cache_kv_heads is None or cache_kv_heads < 1:
+                raise ValueError('cache_layout="hnd" needs cache_kv_heads')
+            if not local:
+                raise ValueError('cache_layout="hnd" uses permuted pages, which need the '
+                                 "local GPU path")
+            if head_range is not None or layer_pages == "fused":
+                raise ValueError('cache_layout="hnd" cannot be combined with head_range or '
+                                 'layer_pages="fused": a permuted page takes neither a slice '
+                                 "nor a tensor set")
+            if block_tokens < 1 or page_elems % (2 * block_tokens * cache_kv_heads) != 0:
+                raise ValueError('with cache_layout="hnd" page_elems is '
+                                 "2*block_tokens*cache_kv_heads*head_dim")
+            self._page_permute = PagePermute(2, block_tokens, cache_kv_heads)
+        elif cache_kv_heads is not None:
+            raise ValueError('cache_kv_heads goes with cache_layout="hnd"')
         if layer_pages == "fused":
             if head_range is not None:
                 raise ValueError('layer_pages="fused" cannot be combined with head_range: '
@@ -305,6 +336,8 @@ class InfiniStoreKVAdapter:
         geo = {}
         if self._page_slice is not None:
             geo["page_slice"] = self._page_slice
+        if self._page_permute is not None:
+            geo["page_permute"] = self._page_permute
         if self.kv_layout == "kv_major":
             geo.update(segments=2, segment_stride=kv_cache.numel() // 2)
         return geo
