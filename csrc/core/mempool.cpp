@@ -57,12 +57,18 @@ void MemoryPool::mark(size_t start, size_t nb, bool used) {
 }
 
 bool MemoryPool::find_run(size_t nb, size_t* out_start) {
-    // Two passes: from cursor to end, then from 0 to cursor.
+    // Two passes: from cursor to end, then from 0 to cursor. A run that
+    // begins before the cursor word may end in or after it: it starts at or
+    // below block 64 * cursor_ - 1, so its last block lies in a word below
+    // cursor_ + ceil((nb - 1) / 64), and the second pass goes that far. For a
+    // single block that is the cursor itself.
     if (find_run_in(nb, cursor_, n_words_, n_blocks_, out_start)) {
         cursor_ = *out_start / 64;
         return true;
     }
-    if (find_run_in(nb, 0, cursor_, n_blocks_, out_start)) {
+    if (cursor_ == 0) return false;  // the first pass saw the whole pool
+    size_t w_end = std::min(n_words_, cursor_ + (nb + 62) / 64);
+    if (find_run_in(nb, 0, w_end, n_blocks_, out_start)) {
         cursor_ = *out_start / 64;
         return true;
     }
@@ -188,6 +194,7 @@ bool MemoryPool::deallocate(void* ptr, size_t size) {
         ERROR("deallocate: invalid pointer %p for pool %d", ptr, pool_idx_);
         return false;
     }
+    if (size == 0) return false;  // no entry has size 0; allocate(0) refuses too
     size_t start = (p - b) / block_size_;
     size_t nb = (size + block_size_ - 1) / block_size_;
     if (start + nb > n_blocks_) return false;
@@ -292,6 +299,30 @@ size_t MM::used_blocks() const {
     size_t t = 0;
     for (auto& p : pools_) t += p->used_blocks();
     return t;
+}
+
+std::vector<CompactionMove> plan_compaction(MM& mm,
+                                            const std::vector<std::pair<void*, size_t>>& movable) {
+    // Move highest addresses first so freed tail space cascades.
+    auto sorted = movable;
+    std::sort(sorted.begin(), sorted.end(),
+              [](const auto& a, const auto& b) { return a.first > b.first; });
+    std::vector<CompactionMove> moves;
+    for (auto& [ptr, size] : sorted) {
+        MemoryPool* owner = nullptr;
+        for (size_t i = 0; i < mm.num_pools(); i++) {
+            MemoryPool* p = mm.pool_mut(static_cast<int>(i));
+            if (p->contains(ptr)) {
+                owner = p;
+                break;
+            }
+        }
+        if (!owner) continue;
+        size_t idx = owner->block_index_of(ptr);
+        void* np = owner->allocate_below(size, idx);
+        if (np) moves.push_back({ptr, np, size, owner->pool_idx()});
+    }
+    return moves;
 }
 
 }  // namespace ifs

@@ -19,6 +19,7 @@
 #include <functional>
 #include <memory>
 #include <string>
+#include <utility>
 #include <vector>
 
 namespace ifs {
@@ -38,7 +39,8 @@ class MemoryPool {
     void* allocate_contiguous(size_t size, size_t n);
     // Compaction helper: allocate only from block range [0, limit_block).
     void* allocate_below(size_t size, size_t limit_block);
-    // Returns false on invalid pointer / double free.
+    // Returns false on invalid pointer / double free / size 0. Any whole
+    // sub-range of used blocks may be freed on its own.
     bool deallocate(void* ptr, size_t size);
 
     size_t block_index_of(void* ptr) const {
@@ -63,6 +65,8 @@ class MemoryPool {
 
     // For compaction planning: snapshot of the used-bitmap.
     const std::vector<uint64_t>& bitmap() const { return bits_; }
+    // Entries on the single-block free list, stale ones included.
+    size_t free_hints() const { return free_stack_.size(); }
 
    private:
     bool run_is_free(size_t start, size_t nb) const;
@@ -138,5 +142,18 @@ class MM {
     std::vector<std::unique_ptr<MemoryPool>> pools_;
     std::vector<ArenaFree> free_fns_;
 };
+
+// Compaction planning: for each (ptr, size), highest address first, try to
+// find a lower slot in the owning pool and mark it used. The old blocks stay
+// used; the caller frees them (or the new ones) once the copy is decided.
+// A pointer that no pool owns is skipped. The caller serialises access to mm.
+struct CompactionMove {
+    void* old_ptr;
+    void* new_ptr;
+    size_t size;
+    int pool_idx;
+};
+std::vector<CompactionMove> plan_compaction(MM& mm,
+                                            const std::vector<std::pair<void*, size_t>>& movable);
 
 }  // namespace ifs

@@ -1780,7 +1780,80 @@ PYBIND11_MODULE(_native, m) {
              [](MemoryPool& p, uintptr_t ptr, size_t size) {
                  return p.deallocate(reinterpret_cast<void*>(ptr), size);
              })
+        .def("allocate_contiguous",
+             [](MemoryPool& p, size_t size, size_t n) {
+                 return reinterpret_cast<uintptr_t>(p.allocate_contiguous(size, n));
+             })
+        .def("allocate_below",
+             [](MemoryPool& p, size_t size, size_t limit_block) {
+                 return reinterpret_cast<uintptr_t>(p.allocate_below(size, limit_block));
+             })
+        .def("largest_free_run", &MemoryPool::largest_free_run)
+        .def("block_index_of",
+             [](MemoryPool& p, uintptr_t ptr) {
+                 return p.block_index_of(reinterpret_cast<void*>(ptr));
+             })
+        .def("bitmap", [](MemoryPool& p) { return p.bitmap(); })
+        .def("free_hints", &MemoryPool::free_hints)
         .def("used_blocks", &MemoryPool::used_blocks)
         .def("total_blocks", &MemoryPool::total_blocks)
         .def("base", [](MemoryPool& p) { return reinterpret_cast<uintptr_t>(p.base()); });
+
+    // MM over host malloc arenas, and compaction planning on it.
+    py::class_<MM>(m, "_TestMM")
+        .def(py::init<>())
+        .def("add_pool",
+             [](MM& mm, size_t size, size_t block_size) {
+                 void* base = malloc(size);
+                 if (!base) throw std::bad_alloc();
+                 return mm.add_pool(base, size, block_size, [](void* p, size_t) { free(p); });
+             })
+        // (pages, calls): pages is [(ptr, pool_idx)] in callback order, or
+        // None if the allocation failed; calls counts the callback's runs.
+        .def("allocate",
+             [](MM& mm, size_t size, size_t n) {
+                 std::vector<std::pair<uintptr_t, int>> pages;
+                 bool ok = mm.allocate(size, n, [&](void* p, int pool) {
+                     pages.emplace_back(reinterpret_cast<uintptr_t>(p), pool);
+                 });
+                 return py::make_tuple(ok ? py::cast(pages) : py::object(py::none()),
+                                       pages.size());
+             })
+        .def("deallocate",
+             [](MM& mm, uintptr_t ptr, size_t size, int pool_idx) {
+                 return mm.deallocate(reinterpret_cast<void*>(ptr), size, pool_idx);
+             })
+        .def("need_extend", &MM::need_extend)
+        .def("used_blocks", &MM::used_blocks)
+        .def("total_blocks", &MM::total_blocks)
+        .def("num_pools", &MM::num_pools)
+        .def("pool_base",
+             [](MM& mm, int i) {
+                 const MemoryPool* p = mm.pool(i);
+                 if (!p) throw std::out_of_range("_TestMM: no such pool");
+                 return reinterpret_cast<uintptr_t>(p->base());
+             })
+        .def("pool_used_blocks",
+             [](MM& mm, int i) {
+                 const MemoryPool* p = mm.pool(i);
+                 if (!p) throw std::out_of_range("_TestMM: no such pool");
+                 return p->used_blocks();
+             })
+        .def("pool_largest_free_run",
+             [](MM& mm, int i) {
+                 const MemoryPool* p = mm.pool(i);
+                 if (!p) throw std::out_of_range("_TestMM: no such pool");
+                 return p->largest_free_run();
+             })
+        // [(ptr, size)] -> [(old, new, size, pool_idx)]; the new slots are
+        // marked used, the old ones stay used.
+        .def("plan_moves", [](MM& mm, const std::vector<std::pair<uintptr_t, size_t>>& movable) {
+            std::vector<std::pair<void*, size_t>> in;
+            for (auto& [p, size] : movable) in.emplace_back(reinterpret_cast<void*>(p), size);
+            std::vector<std::tuple<uintptr_t, uintptr_t, size_t, int>> out;
+            for (auto& mv : plan_compaction(mm, in))
+                out.emplace_back(reinterpret_cast<uintptr_t>(mv.old_ptr),
+                                 reinterpret_cast<uintptr_t>(mv.new_ptr), mv.size, mv.pool_idx);
+            return out;
+        });
 }

@@ -151,12 +151,9 @@ class Shard {
 
     // Compaction planning: for each (ptr, size), try to find a lower slot in
     // the same pool; marks the new slots used. Returns the planned moves.
-    struct Move {
-        void* old_ptr;
-        void* new_ptr;
-        size_t size;
-        int pool_idx;
-    };
+    // The planning itself is ifs::plan_compaction (core/mempool.h), run under
+    // the allocator lock.
+    using Move = CompactionMove;
     std::vector<Move> plan_compaction(const std::vector<std::pair<void*, size_t>>& movable);
 
     // Fragmentation stats (largest contiguous free run in bytes, per pool sum).
