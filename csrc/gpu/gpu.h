@@ -215,12 +215,42 @@ bool launch_transform_blocks_perm(int dev, Stream s, PageCodec codec, PageDir di
 // edges of the lane mapping from it.
 constexpr int kPermThreads = 512;
 
+// --- quantization-error probe ---------------------------------------------------
+// What n client pages of bf16 would lose under `codec` (fp8 or mxfp4), without
+// storing anything: the kernels read the pages and write only
+//   dev_out[(block * parts + part) * kQuantErrFields + k]   (float64),
+// parts = tset.n for a tensor set, else seg.n (1 for a contiguous page). With x
+// an element and x^ what a read returns for it after a write with this codec
+// (bit for bit: the codec headers' functions in the kernels' own expressions):
+//   k = 0  sum x^2          k = 2  max |x - x^|     k = 4  elements whose x or
+//   k = 1  sum (x - x^)^2   k = 3  max |x|                 x^ is not finite
+// Fields 0..3 run over the part's elements with x and x^ both finite; a part of
+// zeros only, or of non-finite elements only, gives exact zeros there. The fp8
+// scale is the PAGE's, one absmax over all parts. No atomics: the summation
+// order depends on the geometry alone (docs/design.md, "quantization-error
+// probe"), so two runs agree bit for bit.
+// Client addressing is the transform launchers': the descriptor is the page, or
+// with seg.n > 1 its first segment, or with tset.n > 0 (seg.n the TOTAL segment
+// count) the byte offset inside every tensor. dev_client_descs is PINNED HOST
+// memory: the kernels read it as every kernel reads its descriptors, and this
+// function reads it to check the alignment. dev_out is device-visible.
+// False before any launch, dev_out untouched and last_error() set, for kNone,
+// a page page_legal refuses, a geometry segments_legal or tensors_legal
+// refuses, a descriptor, base or (applied) stride that is not a multiple of 16,
+// or a grid that does not fit.
+constexpr int kQuantErrFields = 5;
+bool launch_quant_error(int dev, Stream s, PageCodec codec, const uint64_t* dev_client_descs,
+                        int n_blocks, size_t elems_per_block, PageSegments seg,
+                        TensorTable tset /* n == 0: none */, double* dev_out);
+
 // --- block fingerprint ------------------------------------------------------
 // 64-bit position-salted fingerprint per block -> out_hashes[i] (device mem).
 bool launch_hash_blocks(int dev, Stream s, const uint64_t* dev_ptrs, int n_blocks,
                         size_t bytes_per_block, uint64_t* dev_out_hashes);
 
 const char* last_error();
+// For launchers outside gpu.hip (quant_error.hip): record why a call failed.
+void set_last_error(const char* msg);
 
 }  // namespace gpu
 }  // namespace ifs

@@ -23,6 +23,7 @@ namespace gpu {
 
 static thread_local char g_err[256] = {0};
 const char* last_error() { return g_err; }
+void set_last_error(const char* msg) { snprintf(g_err, sizeof(g_err), "%s", msg); }
 
 static bool fail(const char* what, hipError_t e) {
     snprintf(g_err, sizeof(g_err), "%s: %s", what, hipGetErrorString(e));

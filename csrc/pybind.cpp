@@ -161,6 +161,46 @@ struct ScopedStream {
     ScopedStream& operator=(const ScopedStream&) = delete;
 };
 
+// Quantization-error probe (gpu.h): what the n pages at base + offsets[i] (or,
+// with `bases`, at offsets[i] inside every tensor of the set, base being 0)
+// would lose under the codec that wire flag `codec_flag` requests. offsets and
+// segment_stride in BYTES, n_segments the total over all tensors. Descriptors
+// and output sit in pinned host memory: one launch, one sync, no copies. The
+// flat [n, parts, 5] doubles come back. A false from the launcher means that
+// nothing was launched, a refusal: ValueError. out_ptr, when not 0, is a
+// device-visible float64 buffer of that size which takes the output instead
+// (an empty list comes back): a refusal must leave it untouched, which is what
+// tests hand it in for.
+std::vector<double> quant_error_py(uintptr_t base, const std::vector<uint64_t>& offsets,
+                                   size_t elems_per_block, uint32_t codec_flag, int device,
+                                   uint32_t n_segments, uint64_t segment_stride,
+                                   const std::vector<uint64_t>& bases, uintptr_t out_ptr) {
+    const size_t n = offsets.size();
+    if (n == 0) return {};
+    if (!gpu::available()) throw std::runtime_error("quant_error: no GPU available");
+    if (n > static_cast<size_t>(INT32_MAX))
+        throw std::invalid_argument("quant_error: too many blocks");
+    PageCodec codec;
+    if (!page_codec_from_flags(codec_flag, &codec))
+        throw std::invalid_argument("quant_error: more than one quant flag");
+    const size_t parts = bases.empty() ? n_segments : bases.size();
+    const size_t n_out = out_ptr ? 0 : n * parts * gpu::kQuantErrFields;
+    Pinned<uint64_t> h_descs(n);
+    Pinned<double> h_out(n_out + 1);
+    for (size_t i = 0; i < n; i++) h_descs.p[i] = base + offsets[i];
+    ScopedStream st(device);
+    bool ok = gpu::launch_quant_error(
+        device, st.s, codec, h_descs.p, static_cast<int>(n), elems_per_block,
+        PageSegments{n_segments, segment_stride},
+        gpu::TensorTable{bases.data(), static_cast<uint32_t>(bases.size())},
+        out_ptr ? reinterpret_cast<double*>(out_ptr) : h_out.p);
+    if (!ok) throw std::invalid_argument(std::string("quant_error: ") + gpu::last_error());
+    // Drain the stream before the pinned descriptors go away.
+    if (!gpu::stream_sync(st.s))
+        throw std::runtime_error(std::string("quant_error failed: ") + gpu::last_error());
+    return std::vector<double>(h_out.p, h_out.p + n_out);
+}
+
 void require_gpu_and_pairs(const char* what, const std::vector<uint64_t>& src,
                            const std::vector<uint64_t>& dst) {
     if (!gpu::available()) throw std::runtime_error(std::string(what) + ": no GPU available");
@@ -1158,6 +1198,12 @@ PYBIND11_MODULE(_native, m) {
     m.def("gpu_available", [] { return gpu::available(); });
     m.def("gpu_count", [] { return gpu::device_count(); });
     m.def("hash_blocks", &hash_blocks_py, py::call_guard<py::gil_scoped_release>());
+    m.def("quant_error", &quant_error_py, py::arg("base"), py::arg("offsets"),
+          py::arg("elems_per_block"), py::arg("codec_flag"), py::arg("device"),
+          py::arg("n_segments") = 1, py::arg("segment_stride") = 0,
+          py::arg("bases") = std::vector<uint64_t>{}, py::arg("out_ptr") = 0,
+          py::call_guard<py::gil_scoped_release>());
+    m.attr("_QUANT_ERROR_FIELDS") = gpu::kQuantErrFields;
 
     // ---- debug/test surface (kernels, launched directly) ----
     m.def("_dbg_copy_blocks", &copy_blocks_py, py::arg("src_ptrs"), py::arg("dst_ptrs"),

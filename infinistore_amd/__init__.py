@@ -29,6 +29,8 @@ from .lib import (
     snapshot_pool,
     restore_pool,
     fingerprint_blocks,
+    quant_error,
+    QuantErrorFields,
 )
 
 __all__ = [
@@ -55,6 +57,8 @@ __all__ = [
     "restore_pool",
     "compact_pool",
     "fingerprint_blocks",
+    "quant_error",
+    "QuantErrorFields",
 ]
 
 __version__ = "0.1.0"

@@ -26,6 +26,7 @@ SOURCES = [
     CSRC / "core" / "protocol.cpp",
     CSRC / "core" / "mempool.cpp",
     CSRC / "gpu" / "gpu.hip",
+    CSRC / "gpu" / "quant_error.hip",
     CSRC / "fabric" / "verbs_fabric.cpp",
     CSRC / "server" / "shard.cpp",
     CSRC / "server" / "kv_index.cpp",
@@ -35,6 +36,12 @@ SOURCES = [
     CSRC / "client" / "client_verbs.cpp",
     CSRC / "pybind.cpp",
 ]
+
+# Per-file hipcc flags. quant_error.hip: no packed fp32 arithmetic (v_pk_*_f32),
+# so that its x / scale is the scalar multiply (see the file's head).
+HIP_EXTRA_FLAGS = {
+    "quant_error.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+}
 
 HEADERS = sorted((CSRC).rglob("*.h")) + [Path(__file__)]
 
@@ -85,6 +92,7 @@ def _compile_one(src: Path) -> Path:
     if src.suffix == ".hip":
         # Device code: hipcc for gfx950 only.
         cmd = [HIPCC, "-c", str(src), "-o", str(obj), f"--offload-arch={ARCH}"] + _common_flags()
+        cmd += HIP_EXTRA_FLAGS.get(src.name, [])
     else:
         # Host-only C++ (no HIP headers included): plain g++ is much faster.
         cmd = ["g++", "-c", str(src), "-o", str(obj)] + _common_flags()

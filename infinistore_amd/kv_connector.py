@@ -263,6 +263,40 @@ class PagedKVConnector:
                 for k in page_keys]
         return self.conn.delete_keys(keys)
 
+    # -- choosing quant and layer_pages -----------------------------------------
+    def quant_report(self, kv_or_layers, page_offsets, quant: Optional[str], page_elems: int,
+                     segments: int = 1, segment_stride: int = 0) -> List[dict]:
+        """What these pages would lose under `quant` (None: the connector's
+        own), measured on the GPU by lib.quant_error without storing anything.
+        A layer tensor is probed as save_layer stores it; a list of layer
+        tensors as ONE fused page per offset, as save_all_layers stores it,
+        where fp8 keeps one scale across all layers. page_elems, segments and
+        segment_stride describe one layer's part, as in save_layer. Returns one
+        dict per part (a segment of the layer page, or a layer of the fused
+        page), over all pages: snr_db = 10 log10(sum x^2 / sum err^2), inf
+        where nothing is lost; max_abs_err; absmax; nonfinite."""
+        quant = self.quant if quant is None else quant
+        offs = list(page_offsets)
+        if isinstance(kv_or_layers, torch.Tensor):
+            e = lib.quant_error(kv_or_layers.view(-1), offs, page_elems, quant,
+                                segments=segments, segment_stride=segment_stride)
+        else:
+            n = len(kv_or_layers)
+            e = lib.quant_error(None, offs, page_elems * n, quant, segments=segments * n,
+                                segment_stride=segment_stride,
+                                tensors=[t.view(-1) for t in kv_or_layers])
+        f = lib.QUANT_ERROR_FIELDS
+        report = []
+        for p in range(e.shape[1] if len(offs) else 0):
+            sx, se = float(e[:, p, f.sum_sq].sum()), float(e[:, p, f.sum_sq_err].sum())
+            report.append({
+                "snr_db": float("inf") if se == 0 else 10.0 * float(np.log10(sx / se)),
+                "max_abs_err": float(e[:, p, f.max_abs_err].max()),
+                "absmax": float(e[:, p, f.absmax].max()),
+                "nonfinite": int(e[:, p, f.nonfinite].sum()),
+            })
+        return report
+
     # -- internals ------------------------------------------------------------
     def _check_segments(self, kv: torch.Tensor, page_offsets, page_elems: int,
                         segments: int, segment_stride: int, page_slice=None):

@@ -1060,3 +1060,88 @@ def fingerprint_blocks(cache: torch.Tensor, offsets: List[int], page_size: int):
         page_size * es,
         cache.device.index or 0,
     )
+
+
+class QuantErrorFields(NamedTuple):
+    """Indices into the last axis of quant_error's result."""
+
+    sum_sq: int = 0  # sum of x^2
+    sum_sq_err: int = 1  # sum of (x - x^)^2
+    max_abs_err: int = 2  # max |x - x^|
+    absmax: int = 3  # max |x|
+    nonfinite: int = 4  # elements whose x or x^ is not finite
+
+
+QUANT_ERROR_FIELDS = QuantErrorFields()
+
+
+def quant_error(cache: Optional[torch.Tensor], offsets, page_size: int, quant: str,
+                segments: int = 1, segment_stride: int = 0, tensors=None) -> torch.Tensor:
+    """What the pages would lose under ``quant`` ("fp8" or "mxfp4"), measured
+    on the GPU without storing anything: no connection, no server, no pool
+    space. With x an element and x^ what read_pages returns for it after
+    write_pages(quant=quant), bit for bit, the result is a float64 CPU tensor
+    ``[len(offsets), parts, 5]`` holding, per page and part (QuantErrorFields):
+    sum x^2, sum (x - x^)^2, max |x - x^|, max |x| and the number of elements
+    whose x or x^ is not finite; the first four run over the other elements.
+
+    cache, offsets, page_size, segments and segment_stride mean what they mean
+    in write_pages (elements of a bf16 GPU tensor); a part is a segment, or the
+    whole page when segments == 1. tensors=[...] (pass cache=None) is the
+    tensor-set form: the page spans all tensors, offsets are per-tensor
+    element offsets, page_size the whole page, segments the total (default
+    one per tensor), and a part is one tensor's share. The fp8 scale is the
+    PAGE's, so a quiet part that shares a page with a loud one shows a larger
+    relative error than it would alone. Permuted pages need no form of their
+    own: a permutation of whole pieces changes neither the fp8 error nor the
+    mxfp4 groups. Every request write_pages would refuse is a ValueError."""
+    modes = InfinityConnection.QUANT_MODES
+    if quant not in modes:
+        raise ValueError(f"unsupported quant mode {quant!r}")
+    flag, multiple = modes[quant]
+    if (cache is None) == (tensors is None):
+        raise ValueError("pass either cache or tensors")
+    group = [cache] if tensors is None else list(tensors)
+    if not 1 <= len(group) <= InfinityConnection.MAX_PAGE_TENSORS:
+        raise ValueError(f"tensors holds 1..{InfinityConnection.MAX_PAGE_TENSORS} tensors")
+    for t in group:
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.bfloat16:
+            raise ValueError(f"{quant} quant requires bf16 tensors")
+        if not t.is_contiguous():
+            raise ValueError("the tensors must be contiguous")
+        if t.device != group[0].device:
+            raise ValueError("the tensors share one device")
+    es = group[0].element_size()
+    if tensors is not None and segments == 1:
+        segments = len(group)  # not given: one segment per tensor
+    if page_size <= 0 or page_size % multiple != 0:
+        raise ValueError(f"{quant} quant needs page_size % {multiple} == 0")
+    codec = _native._dbg_page_codec(flag, page_size * es)[0]
+    if tensors is None:
+        legal = _native._dbg_segments_legal(codec, page_size * es, segments, segment_stride * es)
+        per = segments
+    else:
+        legal = _native._dbg_tensors_legal(codec, page_size * es, segments,
+                                           segment_stride * es, len(group))
+        per = segments // len(group)
+    if not legal:
+        raise ValueError(f"illegal page geometry for {quant}: a segment is a multiple of "
+                         f"{multiple} elements, segments do not overlap, and the stride "
+                         "keeps them 16-byte aligned")
+    offs = np.asarray(offsets, dtype=np.uint64)
+    if any(t.data_ptr() % 16 for t in group) or (offs * np.uint64(es) % np.uint64(16)).any():
+        raise ValueError(f"{quant} quant needs 16-byte-aligned tensors and page offsets")
+    seg = page_size // segments
+    span = (per - 1) * segment_stride + seg if per > 1 else seg
+    if len(offs) and int(offs.max()) + span > min(t.numel() for t in group):
+        raise ValueError("a page extends outside its tensor")
+    if group[0].device.type != "cuda":
+        raise ValueError("quant_error requires CUDA (ROCm) tensors")
+    parts = len(group) if tensors is not None else segments
+    flat = _native.quant_error(
+        0 if tensors is not None else cache.data_ptr(), [int(o) * es for o in offs],
+        page_size, flag, group[0].device.index or 0, segments,
+        segment_stride * es if per > 1 else 0,
+        [t.data_ptr() for t in group] if tensors is not None else [])
+    return torch.tensor(flat, dtype=torch.float64).reshape(
+        len(offs), parts, len(QUANT_ERROR_FIELDS))

@@ -96,17 +96,18 @@ def main():
                 return 1
             print(f"  [{mode}] {s}")
         objs.append(o)
-    gpu_o = f"{build}/gpu.o"
-    gpu_src = os.path.join(REPO, "csrc/gpu/gpu.hip")
-    if not os.path.exists(gpu_o) or os.path.getmtime(gpu_o) < os.path.getmtime(gpu_src):
-        nosan = [f for f in flags if "sanitize" not in f and f != "-fno-omit-frame-pointer"]
-        r = subprocess.run(["/opt/rocm/bin/hipcc", "-c", "csrc/gpu/gpu.hip", "-o",
-                            gpu_o, "--offload-arch=gfx950"] + nosan,
-                           capture_output=True, text=True, cwd=REPO)
-        if r.returncode:
-            print(r.stderr[:4000])
-            return 1
-    objs.append(gpu_o)
+    for hip in ("gpu", "quant_error"):
+        gpu_o = f"{build}/{hip}.o"
+        gpu_src = os.path.join(REPO, f"csrc/gpu/{hip}.hip")
+        if not os.path.exists(gpu_o) or os.path.getmtime(gpu_o) < os.path.getmtime(gpu_src):
+            nosan = [f for f in flags if "sanitize" not in f and f != "-fno-omit-frame-pointer"]
+            r = subprocess.run(["/opt/rocm/bin/hipcc", "-c", f"csrc/gpu/{hip}.hip", "-o",
+                                gpu_o, "--offload-arch=gfx950"] + nosan,
+                               capture_output=True, text=True, cwd=REPO)
+            if r.returncode:
+                print(r.stderr[:4000])
+                return 1
+        objs.append(gpu_o)
 
     suffix = sysconfig.get_config_var("EXT_SUFFIX")
     out = f"{build}/infinistore_amd/_native{suffix}"
