@@ -402,10 +402,14 @@ int ClientConn::rw_local_packed(char op, const char* keys_blob, size_t blob_len,
                                 uint32_t n_segments, uint64_t segment_stride,
                                 const PackedLocalSliceExt* slice,
                                 const PackedLocalTensorExt* tset,
-                                const PackedLocalPermExt* perm) {
+                                const PackedLocalPermExt* perm,
+                                const PackedLocalXposeExt* xpose) {
     if (out_ticket) *out_ticket = 0;  // 0 = completed synchronously
     if (!connected_) return -1;
     if (perm && perm->rows != 0 && ((slice && slice->n_pieces != 0) || tset))
+        return -INVALID_REQ;  // not together
+    if (xpose && xpose->tokens != 0 &&
+        ((slice && slice->n_pieces != 0) || tset || (perm && perm->rows != 0)))
         return -INVALID_REQ;  // not together
     if (slice && slice->n_pieces != 0 && op != 'R') return -INVALID_REQ;  // read-only
     if (slice && slice->n_pieces != 0 && tset) return -INVALID_REQ;  // not together
@@ -462,7 +466,7 @@ int ClientConn::rw_local_packed(char op, const char* keys_blob, size_t blob_len,
 
     std::vector<uint8_t> body =
         build_packed_local(h, n_segments, segment_stride, offsets, keys_blob, blob_len, slice,
-                           tset, perm);
+                           tset, perm, xpose);
 
     char wire_op = (op == 'W') ? OP_W_FAST : OP_R_FAST;
     static const bool dbg = getenv("IFS_CLIENT_DEBUG") != nullptr;

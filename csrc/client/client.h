@@ -77,7 +77,12 @@ class ClientConn {
                         uint32_t n_segments = 1, uint64_t segment_stride = 0,
                         const PackedLocalSliceExt* slice = nullptr,
                         const PackedLocalTensorExt* tset = nullptr,
-                        const PackedLocalPermExt* perm = nullptr);
+                        const PackedLocalPermExt* perm = nullptr,
+                        const PackedLocalXposeExt* xpose = nullptr);
+    // xpose (null or tokens == 0: not transposed): the tensor holds every page
+    // as a paged-attention cache block (transposed pages, core/page_codec.h).
+    // With a slice, a tensor set or a permutation as well it returns
+    // -INVALID_REQ without sending anything.
     // perm (null or rows == 0: not permuted): the tensor holds every page's
     // pieces with two axes exchanged (permuted pages, core/page_codec.h). With
     // a slice or a tensor set as well it returns -INVALID_REQ without sending

@@ -272,4 +272,64 @@ inline PagePermute permute_from_wire(const PackedLocalPermExt& e) {
     return {e.outer, e.rows, e.cols, e.piece_bytes};
 }
 
+// Transposed pages (docs/design.md, "transposed pages"): on the CLIENT side of
+// a request a page may be the classic paged-attention cache block. A page is
+// outer (1 or 2) halves of tokens x heads x cols elements of elem_bytes; with
+// T, H, C those extents and x_o = inner[o], element (o, t, h, c) sits at
+// element ((o*T + t)*H + h)*C + c of the STORED (canonical) page and at
+// (((o*H + h)*(C/x_o) + c/x_o)*T + t)*x_o + c%x_o of the client page, to which
+// PageSegments then apply as to any page. K of a paged-attention block is
+// x_0 = 16 / elem_bytes ([H, hd/x, T, x]) and V is x_1 = 1 ([H, hd, T]). The
+// bound is a condition, not a tuning value: one (o, h) tile of T x C elements
+// is what a workgroup holds in LDS, with room for further resident workgroups.
+constexpr uint32_t kMaxTransposeTile = 32u << 10;
+
+// Client-side element order of a request's pages; tokens == 0 (the default)
+// is "not transposed".
+struct PageTranspose {
+    uint32_t outer = 0, tokens = 0, heads = 0, cols = 0, elem_bytes = 0;
+    uint32_t inner[2] = {0, 0};
+};
+
+inline bool transpose_is_set(const PageTranspose& x) { return x.tokens != 0; }
+
+// The one predicate for a transposed page (wire parser, server, shard,
+// launchers, bindings, Python client). Both sides move in 16-byte units: a
+// client run of x_o elements is at most one unit and T runs fill whole units,
+// a stored (token, head) row is whole units and, under a transforming codec
+// (bf16 only), whole groups of the codec, so an mxfp4 group never leaves its
+// row. Both x_o are checked whatever outer is. A tile never straddles a client
+// segment, and the page obeys segments_legal like any other.
+inline bool transpose_legal(PageCodec c, size_t page_bytes, const PageTranspose& x,
+                            const PageSegments& seg = {}) {
+    if (x.outer < 1 || x.outer > 2 || x.tokens < 1 || x.heads < 1 || x.cols < 1) return false;
+    if (x.elem_bytes != 1 && x.elem_bytes != 2 && x.elem_bytes != 4) return false;
+    if (page_codec_transforms(c) && x.elem_bytes != kPageElemBytes) return false;
+    for (uint32_t xo : x.inner) {
+        if (xo == 0 || (xo & (xo - 1)) != 0 || xo > 16 || x.cols % xo != 0) return false;
+        if (xo * x.elem_bytes > 16) return false;
+        if (x.tokens % (16 / (xo * x.elem_bytes)) != 0) return false;
+    }
+    const uint64_t row = static_cast<uint64_t>(x.cols) * x.elem_bytes;
+    if (row % 16 != 0 || row % page_codec_info(c).page_multiple != 0) return false;
+    // 128-bit products: five 32-bit values off the wire must not wrap into a match.
+    using u128 = unsigned __int128;
+    if (static_cast<u128>(x.outer) * x.tokens * x.heads * row != static_cast<u128>(page_bytes))
+        return false;
+    if (static_cast<u128>(x.tokens) * row > kMaxTransposeTile) return false;
+    if (seg.n != 1) {
+        if (seg.n == 0 || (static_cast<uint64_t>(x.outer) * x.heads) % seg.n != 0) return false;
+        if (!segments_legal(c, page_bytes, seg.n, seg.stride_bytes)) return false;
+    }
+    return true;
+}
+
+// The geometry as the wire extension carries it, and back.
+inline PackedLocalXposeExt transpose_to_wire(const PageTranspose& x) {
+    return {x.outer, x.tokens, x.heads, x.cols, x.elem_bytes, x.inner[0], x.inner[1], 0};
+}
+inline PageTranspose transpose_from_wire(const PackedLocalXposeExt& e) {
+    return {e.outer, e.tokens, e.heads, e.cols, e.elem_bytes, {e.inner_k, e.inner_v}};
+}
+
 }  // namespace ifs

@@ -163,7 +163,8 @@ std::vector<uint8_t> build_packed_local(PackedLocalHdr h, uint32_t n_segments,
                                         const char* keys_blob, size_t blob_len,
                                         const PackedLocalSliceExt* slice,
                                         const PackedLocalTensorExt* tset,
-                                        const PackedLocalPermExt* perm) {
+                                        const PackedLocalPermExt* perm,
+                                        const PackedLocalXposeExt* xpose) {
     const size_t n = h.n_blocks;
     const bool seg = n_segments != 1;
     const bool sliced = slice && slice->n_pieces != 0;
@@ -175,7 +176,10 @@ std::vector<uint8_t> build_packed_local(PackedLocalHdr h, uint32_t n_segments,
     const size_t seg_ext = seg ? sizeof(PackedLocalSegExt) : 0;
     const size_t slice_end = seg_ext + (sliced ? sizeof(PackedLocalSliceExt) : 0);
     const size_t tset_end = slice_end + (tset ? sizeof(PackedLocalTensorExt) : 0);
-    const size_t ext = tset_end + (permuted ? sizeof(PackedLocalPermExt) : 0);
+    const bool transposed = xpose && xpose->tokens != 0;
+    if (transposed) h.flags |= kLocalFlagTransposed;
+    const size_t perm_end = tset_end + (permuted ? sizeof(PackedLocalPermExt) : 0);
+    const size_t ext = perm_end + (transposed ? sizeof(PackedLocalXposeExt) : 0);
     std::vector<uint8_t> body(sizeof(h) + ext + n * 8 + blob_len);
     memcpy(body.data(), &h, sizeof(h));
     if (seg) {
@@ -185,6 +189,7 @@ std::vector<uint8_t> build_packed_local(PackedLocalHdr h, uint32_t n_segments,
     if (sliced) memcpy(body.data() + sizeof(h) + seg_ext, slice, sizeof(*slice));
     if (tset) memcpy(body.data() + sizeof(h) + slice_end, tset, sizeof(*tset));
     if (permuted) memcpy(body.data() + sizeof(h) + tset_end, perm, sizeof(*perm));
+    if (transposed) memcpy(body.data() + sizeof(h) + perm_end, xpose, sizeof(*xpose));
     if (n) memcpy(body.data() + sizeof(h) + ext, offsets, n * 8);
     if (blob_len) memcpy(body.data() + sizeof(h) + ext + n * 8, keys_blob, blob_len);
     return body;
@@ -203,6 +208,9 @@ bool parse_packed_local(char op, const uint8_t* body, size_t body_len, PackedLoc
     if (has_tset && (h.flags & kLocalFlagSliced)) return false;
     const bool permuted = (h.flags & kLocalFlagPermuted) != 0;
     if (permuted && (h.flags & (kLocalFlagSliced | kLocalFlagTensorSet))) return false;
+    const bool transposed = (h.flags & kLocalFlagTransposed) != 0;
+    if (transposed && (h.flags & (kLocalFlagSliced | kLocalFlagTensorSet | kLocalFlagPermuted)))
+        return false;
     if (h.flags & kLocalFlagSegmented) {
         if (body_len < pos + sizeof(PackedLocalSegExt)) return false;
         PackedLocalSegExt e;
@@ -262,6 +270,22 @@ bool parse_packed_local(char op, const uint8_t* body, size_t body_len, PackedLoc
                            PageSegments{out->n_segments, out->segment_stride}))
             return false;
         out->perm = e;
+    }
+    out->xpose = PackedLocalXposeExt{};
+    if (transposed) {
+        if (body_len < pos + sizeof(PackedLocalXposeExt)) return false;
+        PackedLocalXposeExt e;
+        memcpy(&e, body + pos, sizeof(e));
+        pos += sizeof(e);
+        if (e.rsvd != 0) return false;
+        PageCodec codec = PageCodec::kNone;
+        if (op == OP_W_FAST && !page_codec_from_flags(h.flags, &codec)) return false;
+        // tokens == 0 fails transpose_legal: a parsed request is transposed
+        // exactly when tokens != 0.
+        if (!transpose_legal(codec, h.block_size, transpose_from_wire(e),
+                             PageSegments{out->n_segments, out->segment_stride}))
+            return false;
+        out->xpose = e;
     }
     const size_t n = h.n_blocks;
     const size_t off_end = pos + n * 8;

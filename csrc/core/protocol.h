@@ -58,8 +58,8 @@ constexpr char OP_STATS = 'Q';    // server stats JSON over the wire (extension)
 // Body: PackedLocalHdr, [PackedLocalSegExt when kLocalFlagSegmented is set,]
 // [PackedLocalSliceExt when kLocalFlagSliced is set,] [PackedLocalTensorExt
 // when kLocalFlagTensorSet is set,] [PackedLocalPermExt when
-// kLocalFlagPermuted is set,] u64 offsets[n], NUL-separated key bytes
-// (n keys).
+// kLocalFlagPermuted is set,] [PackedLocalXposeExt when kLocalFlagTransposed
+// is set,] u64 offsets[n], NUL-separated key bytes (n keys).
 constexpr char OP_W_FAST = 'w';
 constexpr char OP_R_FAST = 'r';
 // Shared-memory ring handshake (extension, same-host clients): body is the
@@ -148,6 +148,23 @@ struct PackedLocalPermExt {
 #pragma pack(pop)
 static_assert(sizeof(PackedLocalPermExt) == 24, "packed local permute extension size");
 
+// Follows PackedLocalHdr and every other extension when kLocalFlagTransposed
+// is set: the element order of the request's pages in CLIENT memory
+// (core/page_codec.h, PageTranspose; docs/design.md, "transposed pages").
+#pragma pack(push, 1)
+struct PackedLocalXposeExt {
+    uint32_t outer;
+    uint32_t tokens;
+    uint32_t heads;
+    uint32_t cols;
+    uint32_t elem_bytes;
+    uint32_t inner_k;  // x_0, in elements
+    uint32_t inner_v;  // x_1
+    uint32_t rsvd;     // 0
+};
+#pragma pack(pop)
+static_assert(sizeof(PackedLocalXposeExt) == 32, "packed local transpose extension size");
+
 // OP_TSET_REGISTER body: this header, then n_tensors records in set order.
 #pragma pack(push, 1)
 struct PackedTensorSetHdr {
@@ -196,6 +213,12 @@ constexpr uint32_t kLocalFlagTensorSet = 32;
 // ops). The stored block is the canonical page's. Together with
 // kLocalFlagSliced or kLocalFlagTensorSet it is INVALID_REQ.
 constexpr uint32_t kLocalFlagPermuted = 64;
+// The client holds each page as a paged-attention cache block (per head, K as
+// [cols/x, tokens, x] and V as [cols, tokens]), as the PackedLocalXposeExt
+// after all other extensions says (extension; both packed ops). The stored
+// block is the canonical page's. Together with kLocalFlagSliced,
+// kLocalFlagTensorSet or kLocalFlagPermuted it is INVALID_REQ.
+constexpr uint32_t kLocalFlagTransposed = 128;
 
 std::string op_name(char op);
 
@@ -273,9 +296,11 @@ std::vector<uint8_t> build_packed_local(PackedLocalHdr h, uint32_t n_segments,
                                         const char* keys_blob, size_t blob_len,
                                         const PackedLocalSliceExt* slice = nullptr,
                                         const PackedLocalTensorExt* tset = nullptr,
-                                        const PackedLocalPermExt* perm = nullptr);
+                                        const PackedLocalPermExt* perm = nullptr,
+                                        const PackedLocalXposeExt* xpose = nullptr);
 // (The permute extension and kLocalFlagPermuted are written only for a `perm`
-// with rows != 0, its rsvd as given.)
+// with rows != 0, its rsvd as given; the transpose extension and
+// kLocalFlagTransposed likewise only for an `xpose` with tokens != 0.)
 // (The tensor-set extension and kLocalFlagTensorSet are written only when
 // `tset` is given; the segment extension is then written for n_segments > 1
 // as always, n_segments being the total over all tensors.)
@@ -298,6 +323,7 @@ struct PackedLocalReq {
     bool has_tset = false;
     PackedLocalTensorExt tset{};
     PackedLocalPermExt perm{};  // rows == 0: not permuted
+    PackedLocalXposeExt xpose{};  // tokens == 0: not transposed
     std::vector<std::pair<std::string_view, uint64_t>> blocks;
 };
 // False (the server answers INVALID_REQ) for a truncated body or extension,
@@ -311,7 +337,9 @@ struct PackedLocalReq {
 // segments_legal (same codec choice), and the flag together with
 // kLocalFlagSliced is refused. kLocalFlagPermuted is refused next to either
 // of those two flags, and when permute_legal refuses the geometry for
-// block_size (same codec choice as for segments).
+// block_size (same codec choice as for segments). kLocalFlagTransposed is
+// refused next to any of those three flags, and when transpose_legal refuses
+// the geometry for block_size (same codec choice again).
 bool parse_packed_local(char op, const uint8_t* body, size_t body_len, PackedLocalReq* out);
 
 // Sentinel for duplicate-key allocations: the server returns rkey=0, addr=0

@@ -243,6 +243,31 @@ bool launch_quant_error(int dev, Stream s, PageCodec codec, const uint64_t* dev_
                         int n_blocks, size_t elems_per_block, PageSegments seg,
                         TensorTable tset /* n == 0: none */, double* dev_out);
 
+// --- transposed pages (csrc/gpu/transpose.hip) ---------------------------------
+// The CLIENT side of every page (source of kStore, destination of kLoad) is a
+// paged-attention cache block (core/page_codec.h, PageTranspose; docs/design.md,
+// "transposed pages"), split into seg.n segments on top of that when seg.n > 1;
+// the stored block is byte-identical to the one the contiguous kernels make of
+// the canonical page. One workgroup moves one (block, half, head) tile through
+// LDS with 16-byte accesses on both sides. There is no byte fallback: false
+// before any launch, with last_error() set, for a geometry transpose_legal
+// refuses, unless aligned16 holds (every descriptor pointer is a multiple of
+// 16; the CALLER checks), for a segment stride that is applied and is not a
+// multiple of 16, or for a grid that does not fit.
+bool launch_copy_blocks_xpose(int dev, Stream s, const uint64_t* dev_src, const uint64_t* dev_dst,
+                              int n_blocks, size_t bytes_per_block, bool aligned16,
+                              PageSegments seg, PageDir dir, PageTranspose xp);
+// Transforming codecs (bf16 pages), scales as for launch_transform_blocks: fp8
+// keeps ONE scale per page, mxfp4 indexes codes and scale bytes by the
+// page-global STORED unit.
+bool launch_transform_blocks_xpose(int dev, Stream s, PageCodec codec, PageDir dir,
+                                   const uint64_t* dev_src, const uint64_t* dev_dst,
+                                   float* dev_scales, int n_blocks, size_t elems_per_block,
+                                   bool aligned16, PageSegments seg, PageTranspose xp);
+// Workgroup size of the five transpose kernels: a 16 x 128 bf16 tile is 256
+// 16-byte units, one per lane and side.
+constexpr int kXposeThreads = 256;
+
 // --- block fingerprint ------------------------------------------------------
 // 64-bit position-salted fingerprint per block -> out_hashes[i] (device mem).
 bool launch_hash_blocks(int dev, Stream s, const uint64_t* dev_ptrs, int n_blocks,

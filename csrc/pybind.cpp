@@ -562,6 +562,84 @@ std::pair<bool, std::vector<float>> transform_blocks_perm_py(
     return {ok, scales};
 }
 
+// ---- transposed pages (docs/design.md, "transposed pages") --------------------
+// A transpose from Python: None, or (outer, tokens, heads, cols, elem_bytes,
+// inner_k, inner_v), the extents in elements.
+PageTranspose xpose_from_py(const char* what, const py::object& o) {
+    PageTranspose xp;
+    if (o.is_none()) return xp;
+    py::tuple t = o.cast<py::tuple>();
+    if (t.size() != 7)
+        throw std::invalid_argument(std::string(what) + ": a transpose is (outer, tokens, heads, "
+                                                        "cols, elem_bytes, inner_k, inner_v)");
+    xp.outer = t[0].cast<uint32_t>();
+    xp.tokens = t[1].cast<uint32_t>();
+    xp.heads = t[2].cast<uint32_t>();
+    xp.cols = t[3].cast<uint32_t>();
+    xp.elem_bytes = t[4].cast<uint32_t>();
+    xp.inner[0] = t[5].cast<uint32_t>();
+    xp.inner[1] = t[6].cast<uint32_t>();
+    return xp;
+}
+
+// The two transpose launchers, called directly: one client page pointer and
+// one pool pointer per block. Both return what the launcher returns, so a
+// refusal is False, not an exception; aligned16 is computed from the pointers
+// as Shard::submit_copy does.
+bool copy_blocks_xpose_py(const std::vector<uint64_t>& client, const std::vector<uint64_t>& pool,
+                          size_t bytes_per_block, const py::object& xpose, uint32_t n_segments,
+                          uint64_t segment_stride, bool to_pool, int device) {
+    const char* what = "_dbg_copy_blocks_xpose";
+    const PageTranspose xp = xpose_from_py(what, xpose);
+    require_gpu_and_pairs(what, client, pool);
+    size_t n = client.size();
+    py::gil_scoped_release rel;
+    Pinned<uint64_t> h_client(n ? n : 1), h_pool(n ? n : 1);
+    memcpy(h_client.p, client.data(), n * 8);
+    memcpy(h_pool.p, pool.data(), n * 8);
+    ScopedStream st(device);
+    bool ok = gpu::launch_copy_blocks_xpose(
+        device, st.s, to_pool ? h_client.p : h_pool.p, to_pool ? h_pool.p : h_client.p,
+        static_cast<int>(n), bytes_per_block, all_aligned16(client, pool),
+        PageSegments{n_segments, segment_stride}, to_pool ? PageDir::kStore : PageDir::kLoad, xp);
+    // Always drain the stream before the pinned descriptors go away.
+    if (!gpu::stream_sync(st.s))
+        throw std::runtime_error(std::string(what) + " failed: " + gpu::last_error());
+    return ok;
+}
+
+// to_pool quantizes (the scales come back), else dequantizes (they go in).
+std::pair<bool, std::vector<float>> transform_blocks_xpose_py(
+    int codec_id, bool to_pool, const std::vector<uint64_t>& client,
+    const std::vector<uint64_t>& pool, std::vector<float> scales, size_t elems_per_block,
+    const py::object& xpose, uint32_t n_segments, uint64_t segment_stride, int device) {
+    const char* what = "_dbg_transform_blocks_xpose";
+    const PageCodec codec = codec_from_id(what, codec_id);
+    const PageTranspose xp = xpose_from_py(what, xpose);
+    require_gpu_and_pairs(what, client, pool);
+    size_t n = client.size();
+    const bool page_scale = page_codec_info(codec).page_scale;
+    if (page_scale && !to_pool && scales.size() != n)
+        throw std::invalid_argument(std::string(what) + ": one scale per block");
+    scales.resize(page_scale ? n : 0);
+    py::gil_scoped_release rel;
+    Pinned<uint64_t> h_client(n ? n : 1), h_pool(n ? n : 1);
+    Pinned<float> h_scale(n ? n : 1);
+    memcpy(h_client.p, client.data(), n * 8);
+    memcpy(h_pool.p, pool.data(), n * 8);
+    memcpy(h_scale.p, scales.data(), scales.size() * sizeof(float));
+    ScopedStream st(device);
+    bool ok = gpu::launch_transform_blocks_xpose(
+        device, st.s, codec, to_pool ? PageDir::kStore : PageDir::kLoad,
+        to_pool ? h_client.p : h_pool.p, to_pool ? h_pool.p : h_client.p, h_scale.p,
+        static_cast<int>(n), elems_per_block, all_aligned16(client, pool),
+        PageSegments{n_segments, segment_stride}, xp);
+    if (!gpu::stream_sync(st.s))
+        throw std::runtime_error(std::string(what) + " failed: " + gpu::last_error());
+    if (ok) memcpy(scales.data(), h_scale.p, scales.size() * sizeof(float));
+    return {ok, scales};
+}
+
 // (codec id, stored bytes) of a request with these flags and this logical
 // page size, by the codec table alone (host-only).
 std::pair<int, size_t> page_codec_py(uint32_t flags, size_t page_bytes) {
@@ -638,7 +716,11 @@ py::tuple shard_run_impl(const char* what, int device, int n_streams, int slots_
                          size_t max_descs_per_slot, const py::list& copy_jobs,
                          const py::list& fabric_jobs, int n_threads, double timeout_s,
                          const py::list* slices, const py::list* tsets = nullptr,
-                         const py::list* perms = nullptr) {
+                         const py::list* perms = nullptr, const py::list* xposes = nullptr) {
+    // xposes (null but for _dbg_shard_run_xpose): one entry per copy job, None
+    // or the job's transpose as xpose_from_py takes it.
+    if (xposes && xposes->size() != copy_jobs.size())
+        throw std::invalid_argument(std::string(what) + ": one transpose (or None) per copy job");
     // perms (null but for _dbg_shard_run_perm): one entry per copy job, None
     // or the job's permutation in bytes as perm_from_py takes it.
     if (perms && perms->size() != copy_jobs.size())
@@ -680,6 +762,7 @@ py::tuple shard_run_impl(const char* what, int device, int n_streams, int slots_
         j.scales_off = t[8].cast<size_t>();
         if (slices) j.slice = slice_from_py(what, (*slices)[i], 1);
         if (perms) j.perm = perm_from_py(what, (*perms)[i], 1);
+        if (xposes) j.xpose = xpose_from_py(what, (*xposes)[i]);
         if (tsets && !py::object((*tsets)[i]).is_none()) {
             py::tuple ts = (*tsets)[i].cast<py::tuple>();
             if (ts.size() != 2)
@@ -917,7 +1000,10 @@ PYBIND11_MODULE(_native, m) {
                uint64_t element_size, int block_size, uintptr_t ptr, int device,
                bool sync_response, uint32_t extra_flags, uint32_t n_segments,
                uint64_t segment_stride, const py::object& page_slice,
-               const py::object& page_permute) {
+               const py::object& page_permute, const py::object& page_transpose) {
+                // page_transpose: None or xpose_from_py's tuple of 7
+                const PackedLocalXposeExt xe =
+                    transpose_to_wire(xpose_from_py("rw_local", page_transpose));
                 // page_slice: None or (n_pieces, page, offset, piece, stride)
                 // in elements; reads only (the client refuses it on 'W').
                 const PackedLocalSliceExt sl =
@@ -948,20 +1034,24 @@ PYBIND11_MODULE(_native, m) {
                 return c.rw_local_packed(op.empty() ? 'W' : op[0], blob.data(), blob.size(),
                                          byte_offs.data(), n, block_size, ptr, device,
                                          sync_response, nullptr, extra_flags, n_segments,
-                                         segment_stride * element_size, &sl, nullptr, &pe);
+                                         segment_stride * element_size, &sl, nullptr, &pe, &xe);
             },
             py::arg("op"), py::arg("keys"), py::arg("offsets"), py::arg("element_size"),
             py::arg("block_size"), py::arg("ptr"), py::arg("device"),
             py::arg("sync_response") = false, py::arg("extra_flags") = 0,
             py::arg("n_segments") = 1, py::arg("segment_stride") = 0,
-            py::arg("page_slice") = py::none(), py::arg("page_permute") = py::none())
+            py::arg("page_slice") = py::none(), py::arg("page_permute") = py::none(),
+            py::arg("page_transpose") = py::none())
         .def(
             "rw_local_blob",
             [](ClientConn& c, const std::string& op, py::buffer blob, py::buffer offsets,
                uint64_t element_size, int block_size, uintptr_t ptr, int device,
                bool sync_response, uint32_t extra_flags, uint32_t n_segments,
                uint64_t segment_stride, const py::object& page_slice,
-               const py::object& page_permute) {
+               const py::object& page_permute, const py::object& page_transpose) {
+                // page_transpose: None or xpose_from_py's tuple of 7
+                const PackedLocalXposeExt xe =
+                    transpose_to_wire(xpose_from_py("rw_local", page_transpose));
                 // page_slice: None or (n_pieces, page, offset, piece, stride)
                 // in elements; reads only (the client refuses it on 'W').
                 const PackedLocalSliceExt sl =
@@ -985,19 +1075,22 @@ PYBIND11_MODULE(_native, m) {
                 return c.rw_local_packed(op.empty() ? 'W' : op[0], bp, blen, byte_offs.data(),
                                          n, block_size, ptr, device, sync_response, nullptr,
                                          extra_flags, n_segments,
-                                         segment_stride * element_size, &sl, nullptr, &pe);
+                                         segment_stride * element_size, &sl, nullptr, &pe, &xe);
             },
             py::arg("op"), py::arg("blob"), py::arg("offsets"), py::arg("element_size"),
             py::arg("block_size"), py::arg("ptr"), py::arg("device"),
             py::arg("sync_response") = false, py::arg("extra_flags") = 0,
             py::arg("n_segments") = 1, py::arg("segment_stride") = 0,
-            py::arg("page_slice") = py::none(), py::arg("page_permute") = py::none())
+            py::arg("page_slice") = py::none(), py::arg("page_permute") = py::none(),
+            py::arg("page_transpose") = py::none())
         .def(
             "rw_local_blob_async",
             [](ClientConn& c, const std::string& op, py::buffer blob, py::buffer offsets,
                uint64_t element_size, int block_size, uintptr_t ptr, int device,
                uint32_t n_segments, uint64_t segment_stride, const py::object& page_slice,
-               const py::object& page_permute) {
+               const py::object& page_permute, const py::object& page_transpose) {
+                const PackedLocalXposeExt xe =
+                    transpose_to_wire(xpose_from_py("rw_local", page_transpose));
                 const PackedLocalSliceExt sl =
                     slice_to_wire(slice_from_py("rw_local", page_slice, element_size));
                 const PackedLocalPermExt pe =
@@ -1023,14 +1116,15 @@ PYBIND11_MODULE(_native, m) {
                                             byte_offs.data(), n, block_size, ptr, device,
                                             /*sync_response=*/true, &ticket, 0, n_segments,
                                             segment_stride * element_size, &sl, nullptr,
-                                            &pe);
+                                            &pe, &xe);
                 }
                 return py::make_tuple(ret, ticket);
             },
             py::arg("op"), py::arg("blob"), py::arg("offsets"), py::arg("element_size"),
             py::arg("block_size"), py::arg("ptr"), py::arg("device"),
             py::arg("n_segments") = 1, py::arg("segment_stride") = 0,
-            py::arg("page_slice") = py::none(), py::arg("page_permute") = py::none())
+            py::arg("page_slice") = py::none(), py::arg("page_permute") = py::none(),
+            py::arg("page_transpose") = py::none())
         .def(
             "rw_tset_blob",
             [](ClientConn& c, const std::string& op, py::buffer blob, py::buffer offsets,
@@ -1394,6 +1488,46 @@ PYBIND11_MODULE(_native, m) {
           py::arg("device"), py::arg("n_streams"), py::arg("slots_per_stream"),
           py::arg("max_descs_per_slot"), py::arg("copy_jobs"), py::arg("perms"),
           py::arg("n_threads"), py::arg("timeout_s"), py::arg("slices") = py::none());
+    // The transpose-geometry predicate; the transpose is xpose_from_py's tuple
+    // of 7, the client segments as above.
+    m.def("_dbg_transpose_legal",
+          [](int codec, size_t page_bytes, const py::object& xpose, uint32_t n_segments,
+             uint64_t stride_bytes) {
+              if (xpose.is_none())
+                  throw std::invalid_argument("_dbg_transpose_legal: a transpose is a tuple of 7");
+              return transpose_legal(codec_from_id("_dbg_transpose_legal", codec), page_bytes,
+                                     xpose_from_py("_dbg_transpose_legal", xpose),
+                                     PageSegments{n_segments, stride_bytes});
+          },
+          py::arg("codec"), py::arg("page_bytes"), py::arg("xpose"), py::arg("n_segments") = 1,
+          py::arg("stride_bytes") = 0);
+    m.attr("_MAX_TRANSPOSE_TILE") = kMaxTransposeTile;
+    m.attr("_XPOSE_THREADS") = gpu::kXposeThreads;
+    // The transpose launchers (gpu.h), called directly: one client page pointer
+    // and one pool pointer per block. Return False for what the launcher
+    // refuses; the transform form returns (ok, scales).
+    m.def("_dbg_copy_blocks_xpose", &copy_blocks_xpose_py, py::arg("client_ptrs"),
+          py::arg("pool_ptrs"), py::arg("bytes_per_block"), py::arg("xpose"),
+          py::arg("n_segments") = 1, py::arg("segment_stride") = 0, py::arg("to_pool") = true,
+          py::arg("device") = 0);
+    m.def("_dbg_transform_blocks_xpose", &transform_blocks_xpose_py, py::arg("codec"),
+          py::arg("to_pool"), py::arg("client_ptrs"), py::arg("pool_ptrs"), py::arg("scales"),
+          py::arg("elems_per_block"), py::arg("xpose"), py::arg("n_segments") = 1,
+          py::arg("segment_stride") = 0, py::arg("device") = 0);
+    // _dbg_shard_run's copy jobs, each with a transpose (or None) from `xposes`.
+    m.def("_dbg_shard_run_xpose",
+          [](int device, int n_streams, int slots_per_stream, size_t max_descs_per_slot,
+             const py::list& copy_jobs, const py::list& xposes, int n_threads,
+             double timeout_s) -> py::object {
+              py::tuple out = shard_run_impl("_dbg_shard_run_xpose", device, n_streams,
+                                             slots_per_stream, max_descs_per_slot, copy_jobs,
+                                             py::list(), n_threads, timeout_s, nullptr, nullptr,
+                                             nullptr, &xposes);
+              return out[0];
+          },
+          py::arg("device"), py::arg("n_streams"), py::arg("slots_per_stream"),
+          py::arg("max_descs_per_slot"), py::arg("copy_jobs"), py::arg("xposes"),
+          py::arg("n_threads"), py::arg("timeout_s"));
     // Jobs through a real Shard at small limits. A copy job is (src_ptrs,
     // dst_ptrs, bytes_per_block, codec_id, store, n_segments, segment_stride,
     // scales or None, scales_off), a fabric job (is_put, host buffer,
@@ -1415,7 +1549,20 @@ PYBIND11_MODULE(_native, m) {
              uint32_t flags, uint32_t alloc_mb, py::bytes ipc,
              const std::vector<uint64_t>& offsets, const std::vector<std::string>& keys,
              uint32_t n_segments, uint64_t segment_stride, const py::object& slice,
-             const py::object& tensor_set, const py::object& permute) {
+             const py::object& tensor_set, const py::object& permute,
+             const py::object& transpose) {
+              // None, or xpose_from_py's tuple of 7, optionally with rsvd as
+              // an eighth value
+              PackedLocalXposeExt xe{};
+              if (!transpose.is_none()) {
+                  py::tuple t = transpose.cast<py::tuple>();
+                  if (t.size() != 7 && t.size() != 8)
+                      throw std::invalid_argument(
+                          "_dbg_build_packed_local: a transpose is a tuple of 7 (or 8)");
+                  xe = transpose_to_wire(
+                      xpose_from_py("_dbg_build_packed_local", py::tuple(t[py::slice(0, 7, 1)])));
+                  if (t.size() == 8) xe.rsvd = t[7].cast<uint32_t>();
+              }
               const PackedLocalSliceExt sl =
                   slice_to_wire(slice_from_py("_dbg_build_packed_local", slice, 1));
               // None, or (outer, rows, cols, piece_bytes[, rsvd])
@@ -1463,14 +1610,15 @@ PYBIND11_MODULE(_native, m) {
               }
               auto v = build_packed_local(h, n_segments, segment_stride, offsets.data(),
                                           blob.data(), blob.size(), &sl,
-                                          tensor_set.is_none() ? nullptr : &ts, &pe);
+                                          tensor_set.is_none() ? nullptr : &ts, &pe, &xe);
               return py::bytes(reinterpret_cast<const char*>(v.data()), v.size());
           },
           py::arg("device"), py::arg("pid"), py::arg("base_ptr"), py::arg("base_offset"),
           py::arg("block_size"), py::arg("flags"), py::arg("alloc_mb"), py::arg("ipc"),
           py::arg("offsets"), py::arg("keys"), py::arg("n_segments") = 1,
           py::arg("segment_stride") = 0, py::arg("slice") = py::none(),
-          py::arg("tensor_set") = py::none(), py::arg("permute") = py::none());
+          py::arg("tensor_set") = py::none(), py::arg("permute") = py::none(),
+          py::arg("transpose") = py::none());
     m.def("_dbg_parse_packed_local", [](const std::string& op, py::bytes data) {
         std::string s = data;
         PackedLocalReq r;
@@ -1505,6 +1653,13 @@ PYBIND11_MODULE(_native, m) {
                                           r.perm.piece_bytes);
         else
             d["permute"] = py::none();
+        // None, or the tuple of 7
+        if (r.xpose.tokens)
+            d["transpose"] = py::make_tuple(r.xpose.outer, r.xpose.tokens, r.xpose.heads,
+                                            r.xpose.cols, r.xpose.elem_bytes, r.xpose.inner_k,
+                                            r.xpose.inner_v);
+        else
+            d["transpose"] = py::none();
         py::list offs, keys;
         for (auto& [key, off] : r.blocks) {
             offs.append(off);

@@ -545,6 +545,7 @@ bool parse_packed_local(char op, const uint8_t* body, size_t body_len, Server::L
     v->tset_id = req.tset.set_id;
     v->tset_n = req.tset.n_tensors;
     v->perm = permute_from_wire(req.perm);
+    v->xpose = transpose_from_wire(req.xpose);
     v->ipc = body + offsetof(PackedLocalHdr, ipc);
     v->ipc_len = 64;
     v->blocks = std::move(req.blocks);
@@ -833,10 +834,19 @@ void Server::op_local_write(Conn* c, const LocalView& msg, const ReqCtx& ctx) {
     if (permuted && (tset || !permute_legal(codec, page, msg.perm,
                                             PageSegments{msg.n_segments, msg.segment_stride})))
         return reply_local(c, ctx, INVALID_REQ);
+    // Transposed source pages: likewise, and never next to a permutation.
+    const bool transposed = transpose_is_set(msg.xpose);
+    if (transposed &&
+        (tset || permuted || !transpose_legal(codec, page, msg.xpose,
+                                              PageSegments{msg.n_segments, msg.segment_stride})))
+        return reply_local(c, ctx, INVALID_REQ);
     // The quantize kernels load 16 bytes per lane: every source page must
     // start 16-byte aligned (pool blocks always do), and a 16-byte stride
     // then keeps every segment aligned.
-    if (page_codec_transforms(codec) && !tset) {
+    // The transpose kernels move 16 bytes per lane for every codec.
+    if (transposed && msg.n_segments != 1 && msg.segment_stride % 16 != 0)
+        return reply_local(c, ctx, INVALID_REQ);
+    if ((page_codec_transforms(codec) || transposed) && !tset) {
         for (size_t i = 0; i < nb; i++)
             if ((client_addr + msg.blocks[i].second) % 16 != 0)
                 return reply_local(c, ctx, INVALID_REQ);
@@ -917,6 +927,7 @@ void Server::op_local_write(Conn* c, const LocalView& msg, const ReqCtx& ctx) {
         job.segs_per_tensor = msg.n_segments / static_cast<uint32_t>(tset->bases->size());
     }
     job.perm = msg.perm;
+    job.xpose = msg.xpose;
     job.scales = scales_out;
     for (size_t i = 0; i < n_fresh; i++) {
         auto* e = slab_batch.make();
@@ -1074,6 +1085,12 @@ void Server::op_local_read(Conn* c, const LocalView& msg, const ReqCtx& ctx) {
     const bool permuted = permute_is_set(msg.perm);
     if (permuted && (sliced || tset || !permute_legal(PageCodec::kNone, page, msg.perm, client_seg)))
         return reply_local(c, ctx, INVALID_REQ);
+    // Transposed read: the same, and the 16-byte stride its kernels need.
+    const bool transposed = transpose_is_set(msg.xpose);
+    if (transposed && (sliced || tset || permuted ||
+                       !transpose_legal(PageCodec::kNone, page, msg.xpose, client_seg) ||
+                       (msg.n_segments != 1 && msg.segment_stride % 16 != 0)))
+        return reply_local(c, ctx, INVALID_REQ);
 
     auto tr0 = Clock::now();
     // Group blocks by the shard whose GPU EXECUTES the copy. For same-GPU
@@ -1144,6 +1161,17 @@ void Server::op_local_read(Conn* c, const LocalView& msg, const ReqCtx& ctx) {
                     err = INVALID_REQ;
                     return false;
                 }
+            } else if (transposed) {
+                // As for a permutation: the written size for every codec and
+                // the geometry legal for the entry's codec. The transpose
+                // kernels have no byte path, so the client address is 16-byte
+                // aligned for every codec.
+                if (!stored_matches(e->codec, e->size, page) ||
+                    !transpose_legal(e->codec, page, msg.xpose, client_seg) ||
+                    (client_addr + b.second) % 16 != 0) {
+                    err = INVALID_REQ;
+                    return false;
+                }
             } else if (tset) {
                 // The whole request against the entry's codec (geometry,
                 // aligned bases and offsets), once per codec; the page must
@@ -1184,6 +1212,7 @@ void Server::op_local_read(Conn* c, const LocalView& msg, const ReqCtx& ctx) {
                     it->second.segment_stride = msg.segment_stride;
                     it->second.slice = msg.slice;
                     it->second.perm = msg.perm;
+                    it->second.xpose = msg.xpose;
                     if (tset) {
                         it->second.tensor_bases = tset->bases;
                         it->second.segs_per_tensor =

@@ -159,6 +159,10 @@ class Server {
         // client holds every page's pieces with two axes exchanged. Never
         // together with a slice or a tensor set.
         PagePermute perm;
+        // Transposed pages (packed ops only): xpose.tokens != 0 says that the
+        // client holds every page as a paged-attention cache block. Never
+        // together with a slice, a tensor set or a permutation.
+        PageTranspose xpose;
         const uint8_t* ipc = nullptr;
         size_t ipc_len = 0;
         std::vector<std::pair<std::string_view, uint64_t>> blocks;

@@ -229,6 +229,11 @@ bool Shard::submit_copy(CopyJob&& job) {
     if (permuted && (sliced || tset ||
                      !permute_legal(job.codec, job.bytes_per_block, job.perm, seg)))
         return false;
+    // So is a transpose: next to none of the three.
+    const bool transposed = transpose_is_set(job.xpose);
+    if (transposed && (sliced || tset || permuted ||
+                       !transpose_legal(job.codec, job.bytes_per_block, job.xpose, seg)))
+        return false;
     // A codec with a per-page scale needs one scale slot per block.
     const bool page_scale = page_codec_info(job.codec).page_scale;
     if (page_scale && (!job.scales || job.scales->size() < job.scales_off + n)) return false;
@@ -254,6 +259,7 @@ bool Shard::submit_copy(CopyJob&& job) {
             sub.tensor_bases = job.tensor_bases;
             sub.segs_per_tensor = job.segs_per_tensor;
             sub.perm = job.perm;
+            sub.xpose = job.xpose;
             sub.scales = job.scales;
             sub.scales_off = job.scales_off + off;
             sub.src.assign(job.src.begin() + static_cast<long>(off),
@@ -333,6 +339,32 @@ bool Shard::submit_copy(CopyJob&& job) {
             if (job.done) job.done(true);
             return true;
         }
+        if (transposed) {
+            // Run (o, h, c / x_o, t) of x_o elements: in the client page at
+            // its index in [o][h][c / x_o][t] order, that page being split
+            // into segments, and in the stored page at element (o, t, h, c).
+            const PageTranspose& xp = job.xpose;
+            const bool store = job.dir == PageDir::kStore;
+            const uint64_t T = xp.tokens, H = xp.heads, C = xp.cols;
+            const uint64_t per_seg = job.bytes_per_block / seg.n;
+            for (size_t i = 0; i < n; i++)
+                for (uint64_t oh = 0; oh < xp.outer * H; oh++) {
+                    const uint64_t o = oh / H, h = oh % H;
+                    const uint64_t run = static_cast<uint64_t>(xp.inner[o]) * xp.elem_bytes;
+                    for (uint64_t r = 0; r < C / xp.inner[o] * T; r++) {
+                        const uint64_t cb = r / T, t = r % T;
+                        const uint64_t p = (oh * (C / xp.inner[o]) * T + r) * run;
+                        const uint64_t q = (((o * T + t) * H + h) * C) * xp.elem_bytes + cb * run;
+                        const uint64_t client = (store ? job.src[i] : job.dst[i]) +
+                                                (p / per_seg) * seg.stride_bytes + p % per_seg;
+                        const uint64_t pool = (store ? job.dst[i] : job.src[i]) + q;
+                        memcpy(reinterpret_cast<void*>(store ? pool : client),
+                               reinterpret_cast<const void*>(store ? client : pool), run);
+                    }
+                }
+            if (job.done) job.done(true);
+            return true;
+        }
         const size_t seg_bytes = job.bytes_per_block / seg.n;
         const uint64_t src_step = job.dir == PageDir::kStore ? seg.stride_bytes : seg_bytes;
         const uint64_t dst_step = job.dir == PageDir::kStore ? seg_bytes : seg.stride_bytes;
@@ -368,6 +400,8 @@ bool Shard::submit_copy(CopyJob&& job) {
     // The fp8 and mxfp4 kernels have no byte fallback: they only ever run
     // aligned.
     if (!aligned && transforms) return false;
+    // Neither have the transpose kernels, for any codec.
+    if (!aligned && transposed) return false;
 
     // HIP stream enqueues are thread-safe; each job's ops precede its event
     // in stream order regardless of interleaving with other submitters, so
@@ -403,7 +437,8 @@ bool Shard::submit_copy(CopyJob&& job) {
     // Small aligned batches: descriptors ride in the kernel arguments.
     // (Segmented, sliced and tensor-set jobs always use the pinned-descriptor
     // kernels.)
-    if (aligned && n <= 16 && !transforms && !segmented && !sliced && !tset && !permuted) {
+    if (aligned && n <= 16 && !transforms && !segmented && !sliced && !tset && !permuted &&
+        !transposed) {
         Slot* slot = acquire_slot(sc);
         if (!slot) return false;
         bool ok = gpu::set_device(opt_.device) &&
@@ -481,6 +516,21 @@ bool Shard::submit_copy(CopyJob&& job) {
                                opt_.device, sc.stream, job.codec, job.dir, dsrc, ddst,
                                slot->h_scale, static_cast<int>(take),
                                job.bytes_per_block / kPageElemBytes, aligned, seg, job.perm);
+            }
+        } else if (transposed) {
+            if (!transforms) {
+                ok = ok && gpu::launch_copy_blocks_xpose(opt_.device, sc.stream, dsrc, ddst,
+                                                         static_cast<int>(take),
+                                                         job.bytes_per_block, aligned, seg,
+                                                         job.dir, job.xpose);
+            } else {
+                if (page_scale && job.dir == PageDir::kLoad)
+                    memcpy(slot->h_scale, job.scales->data() + job.scales_off + off,
+                           take * sizeof(float));
+                ok = ok && gpu::launch_transform_blocks_xpose(
+                               opt_.device, sc.stream, job.codec, job.dir, dsrc, ddst,
+                               slot->h_scale, static_cast<int>(take),
+                               job.bytes_per_block / kPageElemBytes, aligned, seg, job.xpose);
             }
         } else if (!transforms) {
             ok = ok && gpu::launch_copy_blocks(opt_.device, sc.stream, dsrc, ddst,

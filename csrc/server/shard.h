@@ -79,6 +79,13 @@ class Shard {
         // Such a job never takes the inline-argument path and carries
         // neither a slice nor a tensor set.
         PagePermute perm;
+        // Transposed pages (core/page_codec.h, transpose_legal): with
+        // xpose.tokens != 0 the CLIENT side holds every page as a
+        // paged-attention cache block, and segments apply to that client
+        // page. Both directions. Such a job never takes the inline-argument
+        // path and carries no slice, tensor set or permutation; on the GPU it
+        // needs 16-byte-aligned pointers and stride for every codec.
+        PageTranspose xpose;
         // Codecs with a per-page scale: block i's scale is
         // (*scales)[scales_off + i], written before done() by kStore and
         // read at submit by kLoad. Fan-out sub-jobs share the vector.

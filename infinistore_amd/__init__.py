@@ -9,6 +9,7 @@ from .lib import (
     InfinityConnection,
     PageSlice,
     PagePermute,
+    PageTranspose,
     TensorSet,
     DisableTorchCaching,
     ClientConfig,
@@ -37,6 +38,7 @@ __all__ = [
     "InfinityConnection",
     "PageSlice",
     "PagePermute",
+    "PageTranspose",
     "TensorSet",
     "DisableTorchCaching",
     "register_server",

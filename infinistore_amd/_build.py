@@ -27,6 +27,7 @@ SOURCES = [
     CSRC / "core" / "mempool.cpp",
     CSRC / "gpu" / "gpu.hip",
     CSRC / "gpu" / "quant_error.hip",
+    CSRC / "gpu" / "transpose.hip",
     CSRC / "fabric" / "verbs_fabric.cpp",
     CSRC / "server" / "shard.cpp",
     CSRC / "server" / "kv_index.cpp",
@@ -39,8 +40,10 @@ SOURCES = [
 
 # Per-file hipcc flags. quant_error.hip: no packed fp32 arithmetic (v_pk_*_f32),
 # so that its x / scale is the scalar multiply (see the file's head).
+_NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 HIP_EXTRA_FLAGS = {
-    "quant_error.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    "quant_error.hip": _NO_PACKED_FP32,
+    "transpose.hip": _NO_PACKED_FP32,
 }
 
 HEADERS = sorted((CSRC).rglob("*.h")) + [Path(__file__)]

@@ -81,6 +81,18 @@ def parse_args():
                    help="with --hnd: what a reader does without permuted pages, "
                         "read whole token-major pages, then permute().contiguous() "
                         "each buffer with torch (inside the timed read)")
+    p.add_argument("--pa", type=int, default=0, metavar="H",
+                   help="transposed pages (local-GPU path): the buffers hold every "
+                        "page as a paged-attention block, K [H, head/x, T, x] with "
+                        "x = 16 / element size and V [H, head, T], head = --pa-head, "
+                        "and the store keeps it token-major; T follows from the page "
+                        "size")
+    p.add_argument("--pa-head", type=int, default=128,
+                   help="elements of one head of one token for --pa")
+    p.add_argument("--pa-baseline", action="store_true",
+                   help="with --pa: what a reader does without transposed pages, "
+                        "read whole token-major pages, then permute().contiguous() "
+                        "K and V of each buffer with torch (inside the timed read)")
     p.add_argument("--verify", action="store_true")
     p.add_argument("--json", action="store_true", help="print a JSON summary")
     p.add_argument("--spawn-server", action="store_true",
@@ -98,6 +110,16 @@ def hnd_geometry(args, page_elems):
     if args.hnd < 1 or args.hnd_head < 1 or page_elems % per_token != 0:
         raise SystemExit("--hnd needs a page of 2 x T x H x --hnd-head elements")
     return lib.PagePermute(2, page_elems // per_token, args.hnd)
+
+
+def pa_geometry(args, page_elems, es):
+    """lib.PageTranspose(T, H, head, x) of --pa, or None."""
+    if not args.pa:
+        return None
+    per_token = 2 * args.pa * args.pa_head
+    if args.pa < 1 or args.pa_head < 1 or page_elems % per_token != 0:
+        raise SystemExit("--pa needs a page of 2 x T x H x --pa-head elements")
+    return lib.PageTranspose(page_elems // per_token, args.pa, args.pa_head, 16 // es)
 
 
 def slice_geometry(args):
@@ -293,12 +315,21 @@ def run_once(args, conn, local, device, bufs=None):
         hnd_outs = [torch.zeros_like(d) for d in dsts]
         torch.cuda.synchronize()
 
+    # --pa: every page is a paged-attention block in the buffers.
+    xpose = pa_geometry(args, page_elems, srcs[0].element_size()) if local else None
+    pa_outs = None
+    if xpose and args.pa_baseline:  # allocated outside the timed window
+        pa_outs = [torch.zeros_like(d) for d in dsts]
+        torch.cuda.synchronize()
+
     def geom(t, permuted=True):  # geometry arguments for sub-tensor t
         g = {}
         if nseg != 1:  # [N, n_pages, page/N]
             g.update(segments=nseg, segment_stride=t.numel() // nseg)
         if perm and permuted:
             g["page_permute"] = perm
+        if xpose and permuted:
+            g["page_transpose"] = xpose
         return g
 
     # ---- write (layer-by-layer batches, like prefill; each step's slice
@@ -309,7 +340,7 @@ def run_once(args, conn, local, device, bufs=None):
         t_idx, _ = sub_of(s0)
         pairs = [(keys[i], sub_of(i)[1]) for i in range(s0, hi)]
         if local:
-            if args.quant or nseg > 1 or perm:
+            if args.quant or nseg > 1 or perm or xpose:
                 conn.write_pages(srcs[t_idx], [p[0] for p in pairs],
                                  [p[1] for p in pairs], page_elems,
                                  quant=args.quant, **geom(srcs[t_idx]))
@@ -350,7 +381,8 @@ def run_once(args, conn, local, device, bufs=None):
                     continue
                 tickets.append(conn.read_pages_async(
                     dsts[t_idx], ks, offs, page_elems,
-                    **geom(dsts[t_idx], permuted=not args.hnd_baseline)))
+                    **geom(dsts[t_idx],
+                           permuted=not (args.hnd_baseline or args.pa_baseline))))
         for tk in tickets:
             conn.wait_read(tk)
         if perm and args.hnd_baseline:
@@ -359,6 +391,18 @@ def run_once(args, conn, local, device, bufs=None):
             for d, o in zip(dsts, hnd_outs):
                 o.view(-1, 2, perm.cols, perm.rows, args.hnd_head).copy_(
                     d.view(-1, 2, perm.rows, perm.cols, args.hnd_head).permute(0, 1, 3, 2, 4))
+            torch.cuda.synchronize()
+        if xpose and args.pa_baseline:
+            # the second pass a reader needs today: token-major pages landed
+            # in the bounce buffers (dsts), the engine wants K as
+            # [H, head/x, T, x] and V as [H, head, T]
+            T_, H_, hd, x = xpose[:4]
+            for d, o in zip(dsts, pa_outs):
+                d5 = d.view(-1, 2, T_, H_, hd)
+                o5 = o.view(-1, 2, H_ * hd * T_)
+                o5[:, 0].view(-1, H_, hd // x, T_, x).copy_(
+                    d5[:, 0].reshape(-1, T_, H_, hd // x, x).permute(0, 2, 3, 1, 4))
+                o5[:, 1].view(-1, H_, hd, T_).copy_(d5[:, 1].permute(0, 2, 3, 1))
             torch.cuda.synchronize()
         if sg and args.slice_baseline:
             # the second pass a reader needs today: pick the heads out of the
@@ -385,7 +429,7 @@ def run_once(args, conn, local, device, bufs=None):
             want = a.view(-1, rows, n_heads, head)[:, :, h0:h1].reshape(-1)
             assert _close(want.cpu(), o.cpu(), args.quant), "verification failed (slice)"
     elif args.verify:
-        for a, b in zip(srcs, hnd_outs or dsts):
+        for a, b in zip(srcs, hnd_outs or pa_outs or dsts):
             assert _close(a.cpu(), b.cpu(), args.quant), "verification failed"
         if nseg > 1:
             _verify_contiguous_read(args, conn, srcs[0], dsts[0].device, keys, page_elems)
@@ -566,6 +610,12 @@ def main():
                      or args.fused_layers):
         raise SystemExit("--hnd needs --local-gpu and no --segments, --slice or "
                          "--fused-layers")
+    if args.pa_baseline and not args.pa:
+        raise SystemExit("--pa-baseline needs --pa")
+    if args.pa and (not args.local_gpu or args.segments != 1 or args.slice
+                    or args.fused_layers or args.hnd):
+        raise SystemExit("--pa needs --local-gpu and no --segments, --slice, "
+                         "--fused-layers or --hnd")
     if args.slice:
         if not args.local_gpu or args.segments != 1:
             raise SystemExit("--slice needs --local-gpu and --segments 1")

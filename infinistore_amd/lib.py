@@ -287,6 +287,24 @@ class PagePermute(NamedTuple):
     cols: int
 
 
+class PageTranspose(NamedTuple):
+    """Client-side element order of a page (docs/design.md, "transposed
+    pages"): the tensor holds each page as a paged-attention cache block, per
+    half and head K as [head_dim // inner_k, tokens, inner_k] and V as
+    [head_dim // inner_v, tokens, inner_v], while the store keeps, and every
+    other reader sees, [halves, tokens, heads, head_dim]. All values are in
+    elements. vLLM's key_cache [blocks, H, hd/x, T, x] and value_cache
+    [blocks, H, hd, T] of a bf16 model: PageTranspose(T, H, hd, 8), with
+    segments=2 when K and V are the two halves of one allocation."""
+
+    tokens: int
+    heads: int
+    head_dim: int
+    inner_k: int
+    inner_v: int = 1
+    halves: int = 2
+
+
 class TensorSet:
     """A registered tensor set (InfinityConnection.register_tensor_set): the
     server-side id and the tensors, which it keeps alive."""
@@ -512,6 +530,45 @@ class InfinityConnection:
                              f"{self.QUANT_MODES[quant][1]} elements")
         return (pm.outer, pm.rows, pm.cols, piece)
 
+    # PageCodec ids of csrc/core/page_codec.h, for the native predicates.
+    QUANT_CODECS = {None: 0, "fp8": 1, "mxfp4": 2}
+
+    def _transpose_arg(self, page_transpose, cache, offsets, page_size: int, segments: int,
+                       segment_stride: int, quant=None, page_slice=None, tensor_set=None,
+                       page_permute=None):
+        """Refuse (ValueError) a transposed request the store cannot serve,
+        before anything is sent; the geometry rule is the native
+        transpose_legal. Returns None, or what the native calls take:
+        (halves, tokens, heads, head_dim, element bytes, inner_k, inner_v)."""
+        if page_transpose is None:
+            return None
+        if page_slice is not None or tensor_set is not None or page_permute is not None:
+            raise ValueError("page_transpose cannot be combined with page_slice, tensor_set "
+                             "or page_permute")
+        if not self.local_connected:
+            raise ValueError("transposed pages use the local GPU path")
+        xp = PageTranspose(*page_transpose)
+        es = cache.element_size()
+        geo = (xp.halves, xp.tokens, xp.heads, xp.head_dim, es, xp.inner_k, xp.inner_v)
+        if min(geo) < 1 or max(geo) >= 1 << 32 or not 0 < page_size < 1 << 60:
+            raise ValueError("PageTranspose values and page_size must be positive")
+        if quant is not None and cache.dtype != torch.bfloat16:
+            raise ValueError(f"{quant} quant requires a bf16 cache")
+        if not _native._dbg_transpose_legal(self.QUANT_CODECS[quant], page_size * es, geo,
+                                            segments, segment_stride * es):
+            raise ValueError(
+                "illegal page transpose: page_size is halves * tokens * heads * head_dim; "
+                "inner_k and inner_v are powers of two dividing head_dim, at most 16 bytes, "
+                "with tokens runs filling whole 16-byte units; a head_dim row is a multiple "
+                "of 16 bytes (of 32 elements with mxfp4); tokens * head_dim is at most "
+                f"{_native._MAX_TRANSPOSE_TILE} bytes; halves * heads is a multiple of segments")
+        offs = np.asarray(offsets, dtype=np.uint64)
+        if (cache.data_ptr() % 16 != 0 or (offs * np.uint64(es) % np.uint64(16)).any()
+                or (segments != 1 and segment_stride * es % 16 != 0)):
+            raise ValueError("transposed pages need a 16-byte-aligned cache, page offsets and "
+                             "segment stride")
+        return geo
+
     @staticmethod
     def _slice_arg(page_slice):
         """The native (n_pieces, page, offset, piece, stride) tuple, or None."""
@@ -617,7 +674,7 @@ class InfinityConnection:
                     sync: bool = False, quant: Optional[str] = None,
                     segments: Optional[int] = None, segment_stride: int = 0,
                     tensor_set=None, page_permute: Optional[PagePermute] = None,
-                    **unsupported):
+                    page_transpose: Optional[PageTranspose] = None, **unsupported):
         """sync=True completes the write in ONE round trip (the response is
         sent when the copy finishes); sync=False (default) returns after the
         server accepts, so uploads overlap compute — call sync() later.
@@ -668,6 +725,15 @@ class InfinityConnection:
         tensor_set; an illegal geometry is a ValueError before anything is
         sent.
 
+        page_transpose=PageTranspose(tokens, heads, head_dim, inner_k):
+        `cache` holds each page as a paged-attention cache block (see
+        PageTranspose) and the stored page is the token-major
+        [halves, tokens, heads, head_dim] one, byte-identical to what a
+        token-major writer stores. Works with every quant and with segments;
+        local path only, not with tensor_set or page_permute; cache, offsets
+        and stride must be 16-byte aligned; an illegal geometry is a
+        ValueError before anything is sent.
+
         Slices are read-only: write_pages has no page_slice parameter, and
         passing one is a ValueError."""
         if "page_slice" in unsupported:
@@ -679,6 +745,9 @@ class InfinityConnection:
             if page_permute is not None:
                 raise ValueError("page_permute cannot be combined with page_slice or "
                                  "tensor_set")
+            if page_transpose is not None:
+                raise ValueError("page_transpose cannot be combined with page_slice, "
+                                 "tensor_set or page_permute")
             if cache is not None:
                 raise ValueError("pass either cache or tensor_set")
             if quant is not None and quant not in self.QUANT_MODES:
@@ -699,6 +768,8 @@ class InfinityConnection:
             raise ValueError("segmented pages use the local GPU path")
         if page_permute is not None and not self.local_connected:
             raise ValueError("permuted pages use the local GPU path")
+        if page_transpose is not None and not self.local_connected:
+            raise ValueError("transposed pages use the local GPU path")
         assert self.local_connected, "write_pages uses the local GPU path"
         flags = 0
         if quant is not None:
@@ -720,17 +791,19 @@ class InfinityConnection:
         self._check_segments(cache.numel(), es, offs, page_size, segments,
                              segment_stride, quant)
         perm = self._permute_arg(page_permute, page_size, segments, quant)
+        xpose = self._transpose_arg(page_transpose, cache, offs, page_size, segments,
+                                    segment_stride, quant, None, None, page_permute)
         if isinstance(keys, (bytes, bytearray, memoryview)):
             ret = self.conn.rw_local_blob(
                 self.OP_W, keys, offs, es, page_size * es,
                 cache.data_ptr(), _remap_device_id(cache), sync, flags,
-                segments, segment_stride, None, perm,
+                segments, segment_stride, None, perm, xpose,
             )
         else:
             ret = self.conn.rw_local_keys(
                 self.OP_W, keys, offs, es, page_size * es,
                 cache.data_ptr(), _remap_device_id(cache), sync, flags,
-                segments, segment_stride, None, perm,
+                segments, segment_stride, None, perm, xpose,
             )
         if ret < 0:
             raise Exception(f"Failed to write to infinistore, ret = {ret}")
@@ -739,7 +812,8 @@ class InfinityConnection:
     def read_pages(self, cache: Optional[torch.Tensor], keys, offsets, page_size: int,
                    segments: Optional[int] = None, segment_stride: int = 0,
                    page_slice: Optional[PageSlice] = None, tensor_set=None,
-                   page_permute: Optional[PagePermute] = None):
+                   page_permute: Optional[PagePermute] = None,
+                   page_transpose: Optional[PageTranspose] = None):
         """segments / segment_stride: scatter each page into that many equal
         pieces of `cache` (see write_pages), however the page was written.
         Local path only.
@@ -761,9 +835,16 @@ class InfinityConnection:
 
         page_permute: deliver each page as [outer, cols, rows, piece] (see
         write_pages), however it was written. page_size must be the written
-        one. Not together with page_slice or tensor_set."""
+        one. Not together with page_slice or tensor_set.
+
+        page_transpose: deliver each page as a paged-attention cache block
+        (see write_pages), however it was written. page_size must be the
+        written one. Not together with page_slice, tensor_set or
+        page_permute."""
         if tensor_set is not None:
             self._permute_arg(page_permute, page_size, 1, None, page_slice, tensor_set)
+            self._transpose_arg(page_transpose, None, None, page_size, 1, 0, None, page_slice,
+                                tensor_set, page_permute)
             offs = self._tensor_set_read_args(cache, tensor_set, offsets, page_size,
                                               segments, segment_stride, page_slice)
             segments = len(tensor_set.tensors) if segments is None else segments
@@ -779,6 +860,8 @@ class InfinityConnection:
         if page_slice is not None and not self.local_connected:
             raise ValueError("sliced reads use the local GPU path")
         perm = self._permute_arg(page_permute, page_size, segments, None, page_slice)
+        xpose = self._transpose_arg(page_transpose, cache, offsets, page_size, segments,
+                                    segment_stride, None, page_slice, None, page_permute)
         es = cache.element_size()
         if self.local_connected:
             offs = np.asarray(offsets, dtype=np.uint64)
@@ -791,13 +874,13 @@ class InfinityConnection:
                 ret = self.conn.rw_local_blob(
                     self.OP_R, keys, offs, es, page_size * es,
                     cache.data_ptr(), _remap_device_id(cache), False, 0,
-                    segments, segment_stride, self._slice_arg(page_slice), perm,
+                    segments, segment_stride, self._slice_arg(page_slice), perm, xpose,
                 )
             else:
                 ret = self.conn.rw_local_keys(
                     self.OP_R, keys, offs, es, page_size * es,
                     cache.data_ptr(), _remap_device_id(cache), False, 0,
-                    segments, segment_stride, self._slice_arg(page_slice), perm,
+                    segments, segment_stride, self._slice_arg(page_slice), perm, xpose,
                 )
         elif self.rdma_connected:
             blocks = [(k, int(o) * es) for k, o in zip(keys, offsets)]
@@ -822,16 +905,19 @@ class InfinityConnection:
     def read_pages_async(self, cache: Optional[torch.Tensor], keys, offsets, page_size: int,
                          segments: Optional[int] = None, segment_stride: int = 0,
                          page_slice: Optional[PageSlice] = None, tensor_set=None,
-                         page_permute: Optional[PagePermute] = None):
+                         page_permute: Optional[PagePermute] = None,
+                         page_transpose: Optional[PageTranspose] = None):
         """Ticketed read (local path, shm ring): pushes the request and
         returns a ticket; call wait_read(ticket) before using the data. Lets
         an engine overlap its own work (or further requests) with the copy —
         e.g. prefetching the next sequence's KV pages while decoding. Falls
         back to a blocking read (ticket 0) when the ring is unavailable.
-        segments / segment_stride / page_slice / tensor_set / page_permute as
-        in read_pages."""
+        segments / segment_stride / page_slice / tensor_set / page_permute /
+        page_transpose as in read_pages."""
         if tensor_set is not None:
             self._permute_arg(page_permute, page_size, 1, None, page_slice, tensor_set)
+            self._transpose_arg(page_transpose, None, None, page_size, 1, 0, None, page_slice,
+                                tensor_set, page_permute)
             offs = self._tensor_set_read_args(cache, tensor_set, offsets, page_size,
                                               segments, segment_stride, page_slice)
             segments = len(tensor_set.tensors) if segments is None else segments
@@ -847,6 +933,8 @@ class InfinityConnection:
         if page_slice is not None and not self.local_connected:
             raise ValueError("sliced reads use the local GPU path")
         perm = self._permute_arg(page_permute, page_size, segments, None, page_slice)
+        xpose = self._transpose_arg(page_transpose, cache, offsets, page_size, segments,
+                                    segment_stride, None, page_slice, None, page_permute)
         assert self.local_connected, "read_pages_async uses the local GPU path"
         es = cache.element_size()
         offs = np.asarray(offsets, dtype=np.uint64)
@@ -860,7 +948,7 @@ class InfinityConnection:
         ret, ticket = self.conn.rw_local_blob_async(
             self.OP_R, keys, offs, es, page_size * es,
             cache.data_ptr(), _remap_device_id(cache), segments, segment_stride,
-            self._slice_arg(page_slice), perm,
+            self._slice_arg(page_slice), perm, xpose,
         )
         if ret < 0:
             raise Exception(f"Failed to read from infinistore, ret = {ret}")

@@ -44,7 +44,7 @@ from typing import Dict, List, Optional, Sequence
 import torch
 
 from .kv_connector import PagedKVConnector, token_page_hashes
-from .lib import PagePermute, PageSlice
+from .lib import PagePermute, PageSlice, PageTranspose
 
 
 class InfiniStoreKVAdapter:
@@ -102,11 +102,18 @@ class InfiniStoreKVAdapter:
             is stored exactly as an "nhd" engine stores it, so engines of
             either layout share keys. Works with both kv_layout values and
             every quant; needs the local path; with head_range or
-            layer_pages="fused" it raises ValueError.
+            layer_pages="fused" it raises ValueError. "pa": the classic
+            paged-attention block, per head K as ``[head/x, block_tokens, x]``
+            with ``x = 16 // element_size`` and V as ``[head, block_tokens]``
+            (vLLM's ``PagedAttention.split_kv_cache`` views), again with
+            ``n_kv = cache_kv_heads``. Every page then travels as a transposed
+            page (docs/design.md, "transposed pages"); ``kv_layout="kv_major"``
+            is vLLM's one ``[2, num_blocks, ...]`` allocation. The same keys,
+            quants and restrictions as for "hnd".
     """
 
     KV_LAYOUTS = ("block_major", "kv_major")
-    CACHE_LAYOUTS = ("nhd", "hnd")
+    CACHE_LAYOUTS = ("nhd", "hnd", "pa")
     LAYER_PAGES = ("per_layer", "fused")
 
     def __init__(self, host: str, port: int, model_tag: str, n_layers: int,
@@ -121,6 +128,7 @@ class InfiniStoreKVAdapter:
         if cache_layout not in self.CACHE_LAYOUTS:
             raise ValueError(f"cache_layout must be one of {self.CACHE_LAYOUTS}")
         self._page_permute = None
+        self._pa = None
         if cache_layout == "hnd":
             if cache_kv_heads is None or cache_kv_heads < 1:
                 raise ValueError('cache_layout="hnd" needs cache_kv_heads')
@@ -135,6 +143,22 @@ class InfiniStoreKVAdapter:
                 raise ValueError('with cache_layout="hnd" page_elems is '
                                  "2*block_tokens*cache_kv_heads*head_dim")
             self._page_permute = PagePermute(2, block_tokens, cache_kv_heads)
+        elif cache_layout == "pa":
+            if cache_kv_heads is None or cache_kv_heads < 1:
+                raise ValueError('cache_layout="pa" needs cache_kv_heads')
+            if not local:
+                raise ValueError('cache_layout="pa" uses transposed pages, which need the '
+                                 "local GPU path")
+            if head_range is not None or layer_pages == "fused":
+                raise ValueError('cache_layout="pa" cannot be combined with head_range or '
+                                 'layer_pages="fused": a transposed page takes neither a '
+                                 "slice nor a tensor set")
+            if block_tokens < 1 or page_elems % (2 * block_tokens * cache_kv_heads) != 0:
+                raise ValueError('with cache_layout="pa" page_elems is '
+                                 "2*block_tokens*cache_kv_heads*head_dim")
+            # (tokens, heads, head_dim); inner_k follows the tensor at each call
+            self._pa = (block_tokens, cache_kv_heads,
+                        page_elems // (2 * block_tokens * cache_kv_heads))
         elif cache_kv_heads is not None:
             raise ValueError('cache_kv_heads goes with cache_layout="hnd"')
         if layer_pages == "fused":
@@ -338,6 +362,8 @@ class InfiniStoreKVAdapter:
             geo["page_slice"] = self._page_slice
         if self._page_permute is not None:
             geo["page_permute"] = self._page_permute
+        if self._pa is not None:
+            geo["page_transpose"] = PageTranspose(*self._pa, 16 // kv_cache.element_size())
         if self.kv_layout == "kv_major":
             geo.update(segments=2, segment_stride=kv_cache.numel() // 2)
         return geo
