@@ -403,13 +403,18 @@ int ClientConn::rw_local_packed(char op, const char* keys_blob, size_t blob_len,
                                 const PackedLocalSliceExt* slice,
                                 const PackedLocalTensorExt* tset,
                                 const PackedLocalPermExt* perm,
-                                const PackedLocalXposeExt* xpose) {
+                                const PackedLocalXposeExt* xpose,
+                                const PackedLocalCastExt* cast) {
     if (out_ticket) *out_ticket = 0;  // 0 = completed synchronously
     if (!connected_) return -1;
     if (perm && perm->rows != 0 && ((slice && slice->n_pieces != 0) || tset))
         return -INVALID_REQ;  // not together
     if (xpose && xpose->tokens != 0 &&
         ((slice && slice->n_pieces != 0) || tset || (perm && perm->rows != 0)))
+        return -INVALID_REQ;  // not together
+    if (cast && cast->elem_type != 0 &&
+        ((slice && slice->n_pieces != 0) || tset || (perm && perm->rows != 0) ||
+         (xpose && xpose->tokens != 0)))
         return -INVALID_REQ;  // not together
     if (slice && slice->n_pieces != 0 && op != 'R') return -INVALID_REQ;  // read-only
     if (slice && slice->n_pieces != 0 && tset) return -INVALID_REQ;  // not together
@@ -466,7 +471,7 @@ int ClientConn::rw_local_packed(char op, const char* keys_blob, size_t blob_len,
 
     std::vector<uint8_t> body =
         build_packed_local(h, n_segments, segment_stride, offsets, keys_blob, blob_len, slice,
-                           tset, perm, xpose);
+                           tset, perm, xpose, cast);
 
     char wire_op = (op == 'W') ? OP_W_FAST : OP_R_FAST;
     static const bool dbg = getenv("IFS_CLIENT_DEBUG") != nullptr;

@@ -78,7 +78,13 @@ class ClientConn {
                         const PackedLocalSliceExt* slice = nullptr,
                         const PackedLocalTensorExt* tset = nullptr,
                         const PackedLocalPermExt* perm = nullptr,
-                        const PackedLocalXposeExt* xpose = nullptr);
+                        const PackedLocalXposeExt* xpose = nullptr,
+                        const PackedLocalCastExt* cast = nullptr);
+    // cast (null or elem_type == 0: not cast): the tensor holds every page as
+    // one-byte e4m3fn codes (cast pages, core/page_codec.h); block_size stays
+    // the logical bf16 size, offsets and the segment stride are client bytes.
+    // With a slice, a tensor set, a permutation or a transpose as well it
+    // returns -INVALID_REQ without sending anything.
     // xpose (null or tokens == 0: not transposed): the tensor holds every page
     // as a paged-attention cache block (transposed pages, core/page_codec.h).
     // With a slice, a tensor set or a permutation as well it returns

@@ -332,4 +332,65 @@ inline PageTranspose transpose_from_wire(const PackedLocalXposeExt& e) {
     return {e.outer, e.tokens, e.heads, e.cols, e.elem_bytes, {e.inner_k, e.inner_v}};
 }
 
+// Cast pages (docs/design.md, "cast pages"): on the CLIENT side of a request a
+// page may hold one-byte OCP e4m3fn codes instead of bf16, element value =
+// code value * scale[h], h being the half (of `halves`, 1 or 2: K and V) the
+// element lies in. The logical page stays the bf16 page: page_bytes, the
+// header's block_size and every stored block are what a bf16 writer holding
+// the dequantized values has, and the client page is page_bytes / 2 bytes.
+// PageSegments apply to the CLIENT page: the segments are equal parts of its
+// bytes and the stride is in client bytes.
+constexpr uint32_t kCastE4m3 = 1;
+
+// Client-side element type of a request's pages; elem_type == 0 (the default)
+// is "not cast".
+struct PageCast {
+    uint32_t elem_type = 0;
+    uint32_t halves = 0;
+    float scale[2] = {0.f, 0.f};
+};
+
+inline bool cast_is_set(const PageCast& c) { return c.elem_type != 0; }
+
+// A scale is a finite, positive, normal float32 (judged on its bits, so no
+// denormal mode bends it).
+inline bool cast_scale_legal(float s) {
+    const uint32_t u = __builtin_bit_cast(uint32_t, s);
+    return u >= 0x00800000u && u < 0x7f800000u;
+}
+
+// The one predicate for a cast page (wire parser, server, shard, launchers,
+// bindings, Python client). The kernels move 8-element lane units (8 client
+// bytes, 16 bf16 bytes) and, under mxfp4, 32-element groups: neither
+// straddles a half or a client segment. With halves == 1 the second scale is
+// still carried and still judged. The stride keeps every client segment
+// 16-byte aligned; it and the segment size are CLIENT bytes.
+inline bool cast_legal(PageCodec c, size_t page_bytes, const PageCast& cast,
+                       const PageSegments& seg = {}) {
+    if (cast.elem_type != kCastE4m3) return false;
+    if (cast.halves != 1 && cast.halves != 2) return false;
+    if (!cast_scale_legal(cast.scale[0]) || !cast_scale_legal(cast.scale[1])) return false;
+    if (page_bytes == 0 || page_bytes % kPageElemBytes != 0 || !page_legal(c, page_bytes))
+        return false;
+    const uint64_t elems = page_bytes / kPageElemBytes;  // = client bytes
+    const uint64_t unit = c == PageCodec::kMxfp4 ? 32 : 8;
+    if (elems % cast.halves != 0 || (elems / cast.halves) % unit != 0) return false;
+    if (seg.n < 1 || seg.n > kMaxPageSegments) return false;
+    if (seg.n > 1) {
+        if (elems % seg.n != 0) return false;
+        const uint64_t cseg = elems / seg.n;
+        if (cseg % unit != 0) return false;
+        if (seg.stride_bytes < cseg || seg.stride_bytes % 16 != 0) return false;
+    }
+    return true;
+}
+
+// The cast as the wire extension carries it, and back.
+inline PackedLocalCastExt cast_to_wire(const PageCast& c) {
+    return {c.elem_type, c.halves, {c.scale[0], c.scale[1]}};
+}
+inline PageCast cast_from_wire(const PackedLocalCastExt& e) {
+    return {e.elem_type, e.halves, {e.scale[0], e.scale[1]}};
+}
+
 }  // namespace ifs

@@ -164,7 +164,8 @@ std::vector<uint8_t> build_packed_local(PackedLocalHdr h, uint32_t n_segments,
                                         const PackedLocalSliceExt* slice,
                                         const PackedLocalTensorExt* tset,
                                         const PackedLocalPermExt* perm,
-                                        const PackedLocalXposeExt* xpose) {
+                                        const PackedLocalXposeExt* xpose,
+                                        const PackedLocalCastExt* cast) {
     const size_t n = h.n_blocks;
     const bool seg = n_segments != 1;
     const bool sliced = slice && slice->n_pieces != 0;
@@ -179,7 +180,10 @@ std::vector<uint8_t> build_packed_local(PackedLocalHdr h, uint32_t n_segments,
     const bool transposed = xpose && xpose->tokens != 0;
     if (transposed) h.flags |= kLocalFlagTransposed;
     const size_t perm_end = tset_end + (permuted ? sizeof(PackedLocalPermExt) : 0);
-    const size_t ext = perm_end + (transposed ? sizeof(PackedLocalXposeExt) : 0);
+    const size_t xpose_end = perm_end + (transposed ? sizeof(PackedLocalXposeExt) : 0);
+    const bool is_cast = cast && cast->elem_type != 0;
+    if (is_cast) h.flags |= kLocalFlagCast;
+    const size_t ext = xpose_end + (is_cast ? sizeof(PackedLocalCastExt) : 0);
     std::vector<uint8_t> body(sizeof(h) + ext + n * 8 + blob_len);
     memcpy(body.data(), &h, sizeof(h));
     if (seg) {
@@ -190,6 +194,7 @@ std::vector<uint8_t> build_packed_local(PackedLocalHdr h, uint32_t n_segments,
     if (tset) memcpy(body.data() + sizeof(h) + slice_end, tset, sizeof(*tset));
     if (permuted) memcpy(body.data() + sizeof(h) + tset_end, perm, sizeof(*perm));
     if (transposed) memcpy(body.data() + sizeof(h) + perm_end, xpose, sizeof(*xpose));
+    if (is_cast) memcpy(body.data() + sizeof(h) + xpose_end, cast, sizeof(*cast));
     if (n) memcpy(body.data() + sizeof(h) + ext, offsets, n * 8);
     if (blob_len) memcpy(body.data() + sizeof(h) + ext + n * 8, keys_blob, blob_len);
     return body;
@@ -211,6 +216,12 @@ bool parse_packed_local(char op, const uint8_t* body, size_t body_len, PackedLoc
     const bool transposed = (h.flags & kLocalFlagTransposed) != 0;
     if (transposed && (h.flags & (kLocalFlagSliced | kLocalFlagTensorSet | kLocalFlagPermuted)))
         return false;
+    // A cast request's segments are of CLIENT bytes: cast_legal judges them
+    // below, once the cast extension has been read.
+    const bool is_cast = (h.flags & kLocalFlagCast) != 0;
+    if (is_cast && (h.flags & (kLocalFlagSliced | kLocalFlagTensorSet | kLocalFlagPermuted |
+                               kLocalFlagTransposed)))
+        return false;
     if (h.flags & kLocalFlagSegmented) {
         if (body_len < pos + sizeof(PackedLocalSegExt)) return false;
         PackedLocalSegExt e;
@@ -219,7 +230,8 @@ bool parse_packed_local(char op, const uint8_t* body, size_t body_len, PackedLoc
         if (e.rsvd != 0) return false;
         PageCodec codec = PageCodec::kNone;
         if (op == OP_W_FAST && !page_codec_from_flags(h.flags, &codec)) return false;
-        if (!has_tset && !segments_legal(codec, h.block_size, e.n_segments, e.segment_stride))
+        if (!has_tset && !is_cast &&
+            !segments_legal(codec, h.block_size, e.n_segments, e.segment_stride))
             return false;
         out->n_segments = e.n_segments;
         out->segment_stride = e.segment_stride;
@@ -286,6 +298,21 @@ bool parse_packed_local(char op, const uint8_t* body, size_t body_len, PackedLoc
                              PageSegments{out->n_segments, out->segment_stride}))
             return false;
         out->xpose = e;
+    }
+    out->cast = PackedLocalCastExt{};
+    if (is_cast) {
+        if (body_len < pos + sizeof(PackedLocalCastExt)) return false;
+        PackedLocalCastExt e;
+        memcpy(&e, body + pos, sizeof(e));
+        pos += sizeof(e);
+        PageCodec codec = PageCodec::kNone;
+        if (op == OP_W_FAST && !page_codec_from_flags(h.flags, &codec)) return false;
+        // elem_type == 0 fails cast_legal: a parsed request is cast exactly
+        // when elem_type != 0.
+        if (!cast_legal(codec, h.block_size, cast_from_wire(e),
+                        PageSegments{out->n_segments, out->segment_stride}))
+            return false;
+        out->cast = e;
     }
     const size_t n = h.n_blocks;
     const size_t off_end = pos + n * 8;

@@ -59,7 +59,8 @@ constexpr char OP_STATS = 'Q';    // server stats JSON over the wire (extension)
 // [PackedLocalSliceExt when kLocalFlagSliced is set,] [PackedLocalTensorExt
 // when kLocalFlagTensorSet is set,] [PackedLocalPermExt when
 // kLocalFlagPermuted is set,] [PackedLocalXposeExt when kLocalFlagTransposed
-// is set,] u64 offsets[n], NUL-separated key bytes (n keys).
+// is set,] [PackedLocalCastExt when kLocalFlagCast is set,] u64 offsets[n],
+// NUL-separated key bytes (n keys).
 constexpr char OP_W_FAST = 'w';
 constexpr char OP_R_FAST = 'r';
 // Shared-memory ring handshake (extension, same-host clients): body is the
@@ -165,6 +166,18 @@ struct PackedLocalXposeExt {
 #pragma pack(pop)
 static_assert(sizeof(PackedLocalXposeExt) == 32, "packed local transpose extension size");
 
+// Follows PackedLocalHdr and every other extension when kLocalFlagCast is set:
+// the element type of the request's pages in CLIENT memory (core/page_codec.h,
+// PageCast; docs/design.md, "cast pages").
+#pragma pack(push, 1)
+struct PackedLocalCastExt {
+    uint32_t elem_type;  // 1: OCP e4m3fn codes
+    uint32_t halves;     // 1 or 2
+    float scale[2];      // element value = code value * scale[half]
+};
+#pragma pack(pop)
+static_assert(sizeof(PackedLocalCastExt) == 16, "packed local cast extension size");
+
 // OP_TSET_REGISTER body: this header, then n_tensors records in set order.
 #pragma pack(push, 1)
 struct PackedTensorSetHdr {
@@ -219,6 +232,14 @@ constexpr uint32_t kLocalFlagPermuted = 64;
 // block is the canonical page's. Together with kLocalFlagSliced,
 // kLocalFlagTensorSet or kLocalFlagPermuted it is INVALID_REQ.
 constexpr uint32_t kLocalFlagTransposed = 128;
+// The client holds each page as one-byte e4m3fn codes with a scale per half,
+// as the PackedLocalCastExt after all other extensions says (extension; both
+// packed ops). block_size stays the LOGICAL bf16 byte count and the stored
+// block is the bf16 page's; the client page is half of it, and a segment
+// extension next to this flag speaks of client bytes. Together with
+// kLocalFlagSliced, kLocalFlagTensorSet, kLocalFlagPermuted or
+// kLocalFlagTransposed it is INVALID_REQ.
+constexpr uint32_t kLocalFlagCast = 256;
 
 std::string op_name(char op);
 
@@ -297,7 +318,10 @@ std::vector<uint8_t> build_packed_local(PackedLocalHdr h, uint32_t n_segments,
                                         const PackedLocalSliceExt* slice = nullptr,
                                         const PackedLocalTensorExt* tset = nullptr,
                                         const PackedLocalPermExt* perm = nullptr,
-                                        const PackedLocalXposeExt* xpose = nullptr);
+                                        const PackedLocalXposeExt* xpose = nullptr,
+                                        const PackedLocalCastExt* cast = nullptr);
+// (The cast extension and kLocalFlagCast are written only for a `cast` with
+// elem_type != 0.)
 // (The permute extension and kLocalFlagPermuted are written only for a `perm`
 // with rows != 0, its rsvd as given; the transpose extension and
 // kLocalFlagTransposed likewise only for an `xpose` with tokens != 0.)
@@ -324,6 +348,7 @@ struct PackedLocalReq {
     PackedLocalTensorExt tset{};
     PackedLocalPermExt perm{};  // rows == 0: not permuted
     PackedLocalXposeExt xpose{};  // tokens == 0: not transposed
+    PackedLocalCastExt cast{};    // elem_type == 0: not cast
     std::vector<std::pair<std::string_view, uint64_t>> blocks;
 };
 // False (the server answers INVALID_REQ) for a truncated body or extension,
@@ -339,7 +364,10 @@ struct PackedLocalReq {
 // of those two flags, and when permute_legal refuses the geometry for
 // block_size (same codec choice as for segments). kLocalFlagTransposed is
 // refused next to any of those three flags, and when transpose_legal refuses
-// the geometry for block_size (same codec choice again).
+// the geometry for block_size (same codec choice again). kLocalFlagCast is
+// refused next to any of those four flags, and when cast_legal refuses the
+// extension for block_size and the segments (same codec choice), which it
+// judges in place of segments_legal.
 bool parse_packed_local(char op, const uint8_t* body, size_t body_len, PackedLocalReq* out);
 
 // Sentinel for duplicate-key allocations: the server returns rkey=0, addr=0

@@ -96,5 +96,15 @@ IFS_FP8_HD uint16_t decode_to_bf16(uint8_t code, float scale) {
     return f32_to_bf16(e4m3_to_f32(code) * scale);
 }
 
+// Cast pages (docs/design.md, "cast pages"): what a store makes of one e4m3fn
+// code of a client's fp8 cache, and what a load hands such a cache for one
+// bf16 element; inv is 1.0f / scale, computed once on the host.
+IFS_FP8_HD uint16_t cast_code_to_bf16(uint8_t code, float scale) {
+    return decode_to_bf16(code, scale);
+}
+IFS_FP8_HD uint8_t cast_bf16_to_code(uint16_t bf16_bits, float inv) {
+    return f32_to_e4m3(bits_f32(static_cast<uint32_t>(bf16_bits) << 16) * inv);
+}
+
 }  // namespace fp8
 }  // namespace ifs

@@ -268,6 +268,31 @@ bool launch_transform_blocks_xpose(int dev, Stream s, PageCodec codec, PageDir d
 // 16-byte units, one per lane and side.
 constexpr int kXposeThreads = 256;
 
+// --- cast pages (csrc/gpu/cast.hip) --------------------------------------------
+// The CLIENT side of every page (source of kStore, destination of kLoad) holds
+// one-byte e4m3fn codes with one scale per half (core/page_codec.h, PageCast;
+// docs/design.md, "cast pages"), in seg.n segments of CLIENT bytes when
+// seg.n > 1; bytes_per_block is the LOGICAL bf16 page, and the stored block is
+// byte-identical to the one the contiguous kernels make of the bf16 page of
+// dequantized values. There is no byte fallback: false before any launch, with
+// last_error() set, for a geometry cast_legal refuses, unless aligned16 holds
+// (every descriptor pointer is a multiple of 16; the CALLER checks), or for a
+// grid that does not fit.
+bool launch_copy_blocks_cast(int dev, Stream s, const uint64_t* dev_src, const uint64_t* dev_dst,
+                             int n_blocks, size_t bytes_per_block, bool aligned16,
+                             PageSegments seg, PageDir dir, PageCast cast);
+// Transforming codecs, scales as for launch_transform_blocks: fp8 keeps ONE
+// scale per page (written by kStore, read by kLoad), mxfp4 indexes codes and
+// scale bytes by the page-global unit. kNone is refused here.
+bool launch_transform_blocks_cast(int dev, Stream s, PageCodec codec, PageDir dir,
+                                  const uint64_t* dev_src, const uint64_t* dev_dst,
+                                  float* dev_scales, int n_blocks, size_t elems_per_block,
+                                  bool aligned16, PageSegments seg, PageCast cast);
+// Workgroup sizes of the cast kernels: the (block, segment, chunk) kernels
+// (plain and mxfp4, whole quads) and the one-workgroup-per-page fp8 pair.
+constexpr int kCastThreads = 256;
+constexpr int kCastFp8Threads = 512;
+
 // --- block fingerprint ------------------------------------------------------
 // 64-bit position-salted fingerprint per block -> out_hashes[i] (device mem).
 bool launch_hash_blocks(int dev, Stream s, const uint64_t* dev_ptrs, int n_blocks,

@@ -640,6 +640,79 @@ std::pair<bool, std::vector<float>> transform_blocks_xpose_py(
     return {ok, scales};
 }
 
+// ---- cast pages (docs/design.md, "cast pages") ---------------------------------
+// A cast from Python: None, or (elem_type, halves, scale_k, scale_v).
+PageCast cast_from_py(const char* what, const py::object& o) {
+    PageCast c;
+    if (o.is_none()) return c;
+    py::tuple t = o.cast<py::tuple>();
+    if (t.size() != 4)
+        throw std::invalid_argument(std::string(what) +
+                                    ": a cast is (elem_type, halves, scale_k, scale_v)");
+    c.elem_type = t[0].cast<uint32_t>();
+    c.halves = t[1].cast<uint32_t>();
+    c.scale[0] = t[2].cast<float>();
+    c.scale[1] = t[3].cast<float>();
+    return c;
+}
+
+// The two cast launchers, called directly, as the transpose ones above:
+// bytes_per_block / elems_per_block are the LOGICAL bf16 page, the segments
+// the client's (in client bytes). Both return what the launcher returns.
+bool copy_blocks_cast_py(const std::vector<uint64_t>& client, const std::vector<uint64_t>& pool,
+                         size_t bytes_per_block, const py::object& cast, uint32_t n_segments,
+                         uint64_t segment_stride, bool to_pool, int device) {
+    const char* what = "_dbg_copy_blocks_cast";
+    const PageCast pc = cast_from_py(what, cast);
+    require_gpu_and_pairs(what, client, pool);
+    size_t n = client.size();
+    py::gil_scoped_release rel;
+    Pinned<uint64_t> h_client(n ? n : 1), h_pool(n ? n : 1);
+    memcpy(h_client.p, client.data(), n * 8);
+    memcpy(h_pool.p, pool.data(), n * 8);
+    ScopedStream st(device);
+    bool ok = gpu::launch_copy_blocks_cast(
+        device, st.s, to_pool ? h_client.p : h_pool.p, to_pool ? h_pool.p : h_client.p,
+        static_cast<int>(n), bytes_per_block, all_aligned16(client, pool),
+        PageSegments{n_segments, segment_stride}, to_pool ? PageDir::kStore : PageDir::kLoad, pc);
+    // Always drain the stream before the pinned descriptors go away.
+    if (!gpu::stream_sync(st.s))
+        throw std::runtime_error(std::string(what) + " failed: " + gpu::last_error());
+    return ok;
+}
+
+// to_pool quantizes (the scales come back), else dequantizes (they go in).
+std::pair<bool, std::vector<float>> transform_blocks_cast_py(
+    int codec_id, bool to_pool, const std::vector<uint64_t>& client,
+    const std::vector<uint64_t>& pool, std::vector<float> scales, size_t elems_per_block,
+    const py::object& cast, uint32_t n_segments, uint64_t segment_stride, int device) {
+    const char* what = "_dbg_transform_blocks_cast";
+    const PageCodec codec = codec_from_id(what, codec_id);
+    const PageCast pc = cast_from_py(what, cast);
+    require_gpu_and_pairs(what, client, pool);
+    size_t n = client.size();
+    const bool page_scale = page_codec_info(codec).page_scale;
+    if (page_scale && !to_pool && scales.size() != n)
+        throw std::invalid_argument(std::string(what) + ": one scale per block");
+    scales.resize(page_scale ? n : 0);
+    py::gil_scoped_release rel;
+    Pinned<uint64_t> h_client(n ? n : 1), h_pool(n ? n : 1);
+    Pinned<float> h_scale(n ? n : 1);
+    memcpy(h_client.p, client.data(), n * 8);
+    memcpy(h_pool.p, pool.data(), n * 8);
+    memcpy(h_scale.p, scales.data(), scales.size() * sizeof(float));
+    ScopedStream st(device);
+    bool ok = gpu::launch_transform_blocks_cast(
+        device, st.s, codec, to_pool ? PageDir::kStore : PageDir::kLoad,
+        to_pool ? h_client.p : h_pool.p, to_pool ? h_pool.p : h_client.p, h_scale.p,
+        static_cast<int>(n), elems_per_block, all_aligned16(client, pool),
+        PageSegments{n_segments, segment_stride}, pc);
+    if (!gpu::stream_sync(st.s))
+        throw std::runtime_error(std::string(what) + " failed: " + gpu::last_error());
+    if (ok) memcpy(scales.data(), h_scale.p, scales.size() * sizeof(float));
+    return {ok, scales};
+}
+
 // (codec id, stored bytes) of a request with these flags and this logical
 // page size, by the codec table alone (host-only).
 std::pair<int, size_t> page_codec_py(uint32_t flags, size_t page_bytes) {
@@ -716,7 +789,12 @@ py::tuple shard_run_impl(const char* what, int device, int n_streams, int slots_
                          size_t max_descs_per_slot, const py::list& copy_jobs,
                          const py::list& fabric_jobs, int n_threads, double timeout_s,
                          const py::list* slices, const py::list* tsets = nullptr,
-                         const py::list* perms = nullptr, const py::list* xposes = nullptr) {
+                         const py::list* perms = nullptr, const py::list* xposes = nullptr,
+                         const py::list* casts = nullptr) {
+    // casts (null but for _dbg_shard_run_cast): one entry per copy job, None
+    // or the job's cast as cast_from_py takes it.
+    if (casts && casts->size() != copy_jobs.size())
+        throw std::invalid_argument(std::string(what) + ": one cast (or None) per copy job");
     // xposes (null but for _dbg_shard_run_xpose): one entry per copy job, None
     // or the job's transpose as xpose_from_py takes it.
     if (xposes && xposes->size() != copy_jobs.size())
@@ -763,6 +841,7 @@ py::tuple shard_run_impl(const char* what, int device, int n_streams, int slots_
         if (slices) j.slice = slice_from_py(what, (*slices)[i], 1);
         if (perms) j.perm = perm_from_py(what, (*perms)[i], 1);
         if (xposes) j.xpose = xpose_from_py(what, (*xposes)[i]);
+        if (casts) j.cast = cast_from_py(what, (*casts)[i]);
         if (tsets && !py::object((*tsets)[i]).is_none()) {
             py::tuple ts = (*tsets)[i].cast<py::tuple>();
             if (ts.size() != 2)
@@ -1000,7 +1079,11 @@ PYBIND11_MODULE(_native, m) {
                uint64_t element_size, int block_size, uintptr_t ptr, int device,
                bool sync_response, uint32_t extra_flags, uint32_t n_segments,
                uint64_t segment_stride, const py::object& page_slice,
-               const py::object& page_permute, const py::object& page_transpose) {
+               const py::object& page_permute, const py::object& page_transpose,
+               const py::object& page_cast) {
+                // page_cast: None or cast_from_py's tuple of 4; block_size is
+                // then the logical bf16 size and element_size the client's 1
+                const PackedLocalCastExt ce = cast_to_wire(cast_from_py("rw_local", page_cast));
                 // page_transpose: None or xpose_from_py's tuple of 7
                 const PackedLocalXposeExt xe =
                     transpose_to_wire(xpose_from_py("rw_local", page_transpose));
@@ -1034,21 +1117,26 @@ PYBIND11_MODULE(_native, m) {
                 return c.rw_local_packed(op.empty() ? 'W' : op[0], blob.data(), blob.size(),
                                          byte_offs.data(), n, block_size, ptr, device,
                                          sync_response, nullptr, extra_flags, n_segments,
-                                         segment_stride * element_size, &sl, nullptr, &pe, &xe);
+                                         segment_stride * element_size, &sl, nullptr, &pe, &xe,
+                                         &ce);
             },
             py::arg("op"), py::arg("keys"), py::arg("offsets"), py::arg("element_size"),
             py::arg("block_size"), py::arg("ptr"), py::arg("device"),
             py::arg("sync_response") = false, py::arg("extra_flags") = 0,
             py::arg("n_segments") = 1, py::arg("segment_stride") = 0,
             py::arg("page_slice") = py::none(), py::arg("page_permute") = py::none(),
-            py::arg("page_transpose") = py::none())
+            py::arg("page_transpose") = py::none(), py::arg("page_cast") = py::none())
         .def(
             "rw_local_blob",
             [](ClientConn& c, const std::string& op, py::buffer blob, py::buffer offsets,
                uint64_t element_size, int block_size, uintptr_t ptr, int device,
                bool sync_response, uint32_t extra_flags, uint32_t n_segments,
                uint64_t segment_stride, const py::object& page_slice,
-               const py::object& page_permute, const py::object& page_transpose) {
+               const py::object& page_permute, const py::object& page_transpose,
+               const py::object& page_cast) {
+                // page_cast: None or cast_from_py's tuple of 4; block_size is
+                // then the logical bf16 size and element_size the client's 1
+                const PackedLocalCastExt ce = cast_to_wire(cast_from_py("rw_local", page_cast));
                 // page_transpose: None or xpose_from_py's tuple of 7
                 const PackedLocalXposeExt xe =
                     transpose_to_wire(xpose_from_py("rw_local", page_transpose));
@@ -1075,20 +1163,23 @@ PYBIND11_MODULE(_native, m) {
                 return c.rw_local_packed(op.empty() ? 'W' : op[0], bp, blen, byte_offs.data(),
                                          n, block_size, ptr, device, sync_response, nullptr,
                                          extra_flags, n_segments,
-                                         segment_stride * element_size, &sl, nullptr, &pe, &xe);
+                                         segment_stride * element_size, &sl, nullptr, &pe, &xe,
+                                         &ce);
             },
             py::arg("op"), py::arg("blob"), py::arg("offsets"), py::arg("element_size"),
             py::arg("block_size"), py::arg("ptr"), py::arg("device"),
             py::arg("sync_response") = false, py::arg("extra_flags") = 0,
             py::arg("n_segments") = 1, py::arg("segment_stride") = 0,
             py::arg("page_slice") = py::none(), py::arg("page_permute") = py::none(),
-            py::arg("page_transpose") = py::none())
+            py::arg("page_transpose") = py::none(), py::arg("page_cast") = py::none())
         .def(
             "rw_local_blob_async",
             [](ClientConn& c, const std::string& op, py::buffer blob, py::buffer offsets,
                uint64_t element_size, int block_size, uintptr_t ptr, int device,
                uint32_t n_segments, uint64_t segment_stride, const py::object& page_slice,
-               const py::object& page_permute, const py::object& page_transpose) {
+               const py::object& page_permute, const py::object& page_transpose,
+               const py::object& page_cast) {
+                const PackedLocalCastExt ce = cast_to_wire(cast_from_py("rw_local", page_cast));
                 const PackedLocalXposeExt xe =
                     transpose_to_wire(xpose_from_py("rw_local", page_transpose));
                 const PackedLocalSliceExt sl =
@@ -1116,7 +1207,7 @@ PYBIND11_MODULE(_native, m) {
                                             byte_offs.data(), n, block_size, ptr, device,
                                             /*sync_response=*/true, &ticket, 0, n_segments,
                                             segment_stride * element_size, &sl, nullptr,
-                                            &pe, &xe);
+                                            &pe, &xe, &ce);
                 }
                 return py::make_tuple(ret, ticket);
             },
@@ -1124,7 +1215,7 @@ PYBIND11_MODULE(_native, m) {
             py::arg("block_size"), py::arg("ptr"), py::arg("device"),
             py::arg("n_segments") = 1, py::arg("segment_stride") = 0,
             py::arg("page_slice") = py::none(), py::arg("page_permute") = py::none(),
-            py::arg("page_transpose") = py::none())
+            py::arg("page_transpose") = py::none(), py::arg("page_cast") = py::none())
         .def(
             "rw_tset_blob",
             [](ClientConn& c, const std::string& op, py::buffer blob, py::buffer offsets,
@@ -1528,6 +1619,67 @@ PYBIND11_MODULE(_native, m) {
           py::arg("device"), py::arg("n_streams"), py::arg("slots_per_stream"),
           py::arg("max_descs_per_slot"), py::arg("copy_jobs"), py::arg("xposes"),
           py::arg("n_threads"), py::arg("timeout_s"));
+    // The cast predicate; the cast is cast_from_py's tuple of 4, the client
+    // segments (in client bytes) as above.
+    m.def("_dbg_cast_legal",
+          [](int codec, size_t page_bytes, const py::object& cast, uint32_t n_segments,
+             uint64_t stride_bytes) {
+              if (cast.is_none())
+                  throw std::invalid_argument("_dbg_cast_legal: a cast is a tuple of 4");
+              return cast_legal(codec_from_id("_dbg_cast_legal", codec), page_bytes,
+                                cast_from_py("_dbg_cast_legal", cast),
+                                PageSegments{n_segments, stride_bytes});
+          },
+          py::arg("codec"), py::arg("page_bytes"), py::arg("cast"), py::arg("n_segments") = 1,
+          py::arg("stride_bytes") = 0);
+    m.attr("_CAST_THREADS") = gpu::kCastThreads;
+    m.attr("_CAST_FP8_THREADS") = gpu::kCastFp8Threads;
+    // The cast launchers (gpu.h), called directly: one client page pointer and
+    // one pool pointer per block. Return False for what the launcher refuses;
+    // the transform form returns (ok, scales).
+    m.def("_dbg_copy_blocks_cast", &copy_blocks_cast_py, py::arg("client_ptrs"),
+          py::arg("pool_ptrs"), py::arg("bytes_per_block"), py::arg("cast"),
+          py::arg("n_segments") = 1, py::arg("segment_stride") = 0, py::arg("to_pool") = true,
+          py::arg("device") = 0);
+    m.def("_dbg_transform_blocks_cast", &transform_blocks_cast_py, py::arg("codec"),
+          py::arg("to_pool"), py::arg("client_ptrs"), py::arg("pool_ptrs"), py::arg("scales"),
+          py::arg("elems_per_block"), py::arg("cast"), py::arg("n_segments") = 1,
+          py::arg("segment_stride") = 0, py::arg("device") = 0);
+    // _dbg_shard_run's copy jobs, each with a cast (or None) from `casts`.
+    m.def("_dbg_shard_run_cast",
+          [](int device, int n_streams, int slots_per_stream, size_t max_descs_per_slot,
+             const py::list& copy_jobs, const py::list& casts, int n_threads,
+             double timeout_s) -> py::object {
+              py::tuple out = shard_run_impl("_dbg_shard_run_cast", device, n_streams,
+                                             slots_per_stream, max_descs_per_slot, copy_jobs,
+                                             py::list(), n_threads, timeout_s, nullptr, nullptr,
+                                             nullptr, nullptr, &casts);
+              return out[0];
+          },
+          py::arg("device"), py::arg("n_streams"), py::arg("slots_per_stream"),
+          py::arg("max_descs_per_slot"), py::arg("copy_jobs"), py::arg("casts"),
+          py::arg("n_threads"), py::arg("timeout_s"));
+    // The scalar rules of a cast page on the host (csrc/gpu/fp8_codec.h): codes
+    // -> bf16 bits under a scale, and bf16 bits -> codes under inv = 1 / scale.
+    m.def("_dbg_cast_store", [](py::buffer codes, float scale) {
+        py::buffer_info in = codes.request();
+        if (in.itemsize != 1) throw std::invalid_argument("_dbg_cast_store takes a uint8 buffer");
+        const uint8_t* c = static_cast<const uint8_t*>(in.ptr);
+        std::vector<uint16_t> out(static_cast<size_t>(in.size));
+        for (size_t i = 0; i < out.size(); i++) out[i] = fp8::cast_code_to_bf16(c[i], scale);
+        return py::bytes(reinterpret_cast<const char*>(out.data()), out.size() * 2);
+    });
+    m.def("_dbg_cast_load", [](py::buffer bf16_bits, float scale) {
+        py::buffer_info in = bf16_bits.request();
+        if (in.itemsize != 2)
+            throw std::invalid_argument("_dbg_cast_load takes the uint16 bits of bf16 values");
+        const uint16_t* h = static_cast<const uint16_t*>(in.ptr);
+        const float inv = 1.0f / scale;
+        std::string out(static_cast<size_t>(in.size), '\0');
+        for (size_t i = 0; i < out.size(); i++)
+            out[i] = static_cast<char>(fp8::cast_bf16_to_code(h[i], inv));
+        return py::bytes(out);
+    });
     // Jobs through a real Shard at small limits. A copy job is (src_ptrs,
     // dst_ptrs, bytes_per_block, codec_id, store, n_segments, segment_stride,
     // scales or None, scales_off), a fabric job (is_put, host buffer,
@@ -1550,7 +1702,10 @@ PYBIND11_MODULE(_native, m) {
              const std::vector<uint64_t>& offsets, const std::vector<std::string>& keys,
              uint32_t n_segments, uint64_t segment_stride, const py::object& slice,
              const py::object& tensor_set, const py::object& permute,
-             const py::object& transpose) {
+             const py::object& transpose, const py::object& cast) {
+              // None, or cast_from_py's tuple of 4, written as given
+              const PackedLocalCastExt ce =
+                  cast_to_wire(cast_from_py("_dbg_build_packed_local", cast));
               // None, or xpose_from_py's tuple of 7, optionally with rsvd as
               // an eighth value
               PackedLocalXposeExt xe{};
@@ -1610,7 +1765,8 @@ PYBIND11_MODULE(_native, m) {
               }
               auto v = build_packed_local(h, n_segments, segment_stride, offsets.data(),
                                           blob.data(), blob.size(), &sl,
-                                          tensor_set.is_none() ? nullptr : &ts, &pe, &xe);
+                                          tensor_set.is_none() ? nullptr : &ts, &pe, &xe,
+                                          &ce);
               return py::bytes(reinterpret_cast<const char*>(v.data()), v.size());
           },
           py::arg("device"), py::arg("pid"), py::arg("base_ptr"), py::arg("base_offset"),
@@ -1618,7 +1774,7 @@ PYBIND11_MODULE(_native, m) {
           py::arg("offsets"), py::arg("keys"), py::arg("n_segments") = 1,
           py::arg("segment_stride") = 0, py::arg("slice") = py::none(),
           py::arg("tensor_set") = py::none(), py::arg("permute") = py::none(),
-          py::arg("transpose") = py::none());
+          py::arg("transpose") = py::none(), py::arg("cast") = py::none());
     m.def("_dbg_parse_packed_local", [](const std::string& op, py::bytes data) {
         std::string s = data;
         PackedLocalReq r;
@@ -1660,6 +1816,12 @@ PYBIND11_MODULE(_native, m) {
                                             r.xpose.inner_v);
         else
             d["transpose"] = py::none();
+        // None, or the tuple of 4
+        if (r.cast.elem_type)
+            d["cast"] = py::make_tuple(r.cast.elem_type, r.cast.halves, r.cast.scale[0],
+                                       r.cast.scale[1]);
+        else
+            d["cast"] = py::none();
         py::list offs, keys;
         for (auto& [key, off] : r.blocks) {
             offs.append(off);

@@ -546,6 +546,7 @@ bool parse_packed_local(char op, const uint8_t* body, size_t body_len, Server::L
     v->tset_n = req.tset.n_tensors;
     v->perm = permute_from_wire(req.perm);
     v->xpose = transpose_from_wire(req.xpose);
+    v->cast = cast_from_wire(req.cast);
     v->ipc = body + offsetof(PackedLocalHdr, ipc);
     v->ipc_len = 64;
     v->blocks = std::move(req.blocks);
@@ -821,10 +822,18 @@ void Server::op_local_write(Conn* c, const LocalView& msg, const ReqCtx& ctx) {
     if (!page_legal(codec, page)) return reply_local(c, ctx, INVALID_REQ);
     // Segmented source pages: the geometry rules, the stride's alignment for
     // transforming codecs among them, are segments_legal's.
+    // Cast source pages: cast_legal is the whole geometry rule, the segments
+    // of client bytes included, and nothing else may accompany it.
+    const bool is_cast = cast_is_set(msg.cast);
     if (tset) {
         // tensors_legal, every part inside its tensor, aligned bases and
         // offsets for a transforming codec.
-        if (!tensor_set_request_ok(*tset, msg, codec)) return reply_local(c, ctx, INVALID_REQ);
+        if (is_cast || !tensor_set_request_ok(*tset, msg, codec))
+            return reply_local(c, ctx, INVALID_REQ);
+    } else if (is_cast) {
+        if (permute_is_set(msg.perm) || transpose_is_set(msg.xpose) ||
+            !cast_legal(codec, page, msg.cast, PageSegments{msg.n_segments, msg.segment_stride}))
+            return reply_local(c, ctx, INVALID_REQ);
     } else if (!segments_legal(codec, page, msg.n_segments, msg.segment_stride)) {
         return reply_local(c, ctx, INVALID_REQ);
     }
@@ -846,7 +855,8 @@ void Server::op_local_write(Conn* c, const LocalView& msg, const ReqCtx& ctx) {
     // The transpose kernels move 16 bytes per lane for every codec.
     if (transposed && msg.n_segments != 1 && msg.segment_stride % 16 != 0)
         return reply_local(c, ctx, INVALID_REQ);
-    if ((page_codec_transforms(codec) || transposed) && !tset) {
+    // So do the cast kernels (8 bytes per lane on the client, 16 in the pool).
+    if ((page_codec_transforms(codec) || transposed || is_cast) && !tset) {
         for (size_t i = 0; i < nb; i++)
             if ((client_addr + msg.blocks[i].second) % 16 != 0)
                 return reply_local(c, ctx, INVALID_REQ);
@@ -928,6 +938,7 @@ void Server::op_local_write(Conn* c, const LocalView& msg, const ReqCtx& ctx) {
     }
     job.perm = msg.perm;
     job.xpose = msg.xpose;
+    job.cast = msg.cast;
     job.scales = scales_out;
     for (size_t i = 0; i < n_fresh; i++) {
         auto* e = slab_batch.make();
@@ -1063,8 +1074,16 @@ void Server::op_local_read(Conn* c, const LocalView& msg, const ReqCtx& ctx) {
     // Segmented destination pages. Plain rules here; a compressed entry is
     // checked against its own codec's rules in the sweep, next to
     // stored_matches.
+    // Cast destination pages: cast_legal in place of segments_legal (the
+    // segments are of client bytes), and nothing else next to it.
+    const bool is_cast = cast_is_set(msg.cast);
     if (tset) {
-        if (!tensor_set_request_ok(*tset, msg, PageCodec::kNone))
+        if (is_cast || !tensor_set_request_ok(*tset, msg, PageCodec::kNone))
+            return reply_local(c, ctx, INVALID_REQ);
+    } else if (is_cast) {
+        if (slice_is_set(msg.slice) || permute_is_set(msg.perm) || transpose_is_set(msg.xpose) ||
+            !cast_legal(PageCodec::kNone, page, msg.cast,
+                        PageSegments{msg.n_segments, msg.segment_stride}))
             return reply_local(c, ctx, INVALID_REQ);
     } else if (!segments_legal(PageCodec::kNone, page, msg.n_segments, msg.segment_stride)) {
         return reply_local(c, ctx, INVALID_REQ);
@@ -1172,6 +1191,16 @@ void Server::op_local_read(Conn* c, const LocalView& msg, const ReqCtx& ctx) {
                     err = INVALID_REQ;
                     return false;
                 }
+            } else if (is_cast) {
+                // As for a transpose: the written size for every codec, the
+                // cast legal for the entry's codec, and a 16-byte-aligned
+                // client address, because the cast kernels have no byte path.
+                if (!stored_matches(e->codec, e->size, page) ||
+                    !cast_legal(e->codec, page, msg.cast, client_seg) ||
+                    (client_addr + b.second) % 16 != 0) {
+                    err = INVALID_REQ;
+                    return false;
+                }
             } else if (tset) {
                 // The whole request against the entry's codec (geometry,
                 // aligned bases and offsets), once per codec; the page must
@@ -1213,6 +1242,7 @@ void Server::op_local_read(Conn* c, const LocalView& msg, const ReqCtx& ctx) {
                     it->second.slice = msg.slice;
                     it->second.perm = msg.perm;
                     it->second.xpose = msg.xpose;
+                    it->second.cast = msg.cast;
                     if (tset) {
                         it->second.tensor_bases = tset->bases;
                         it->second.segs_per_tensor =

@@ -163,6 +163,11 @@ class Server {
         // client holds every page as a paged-attention cache block. Never
         // together with a slice, a tensor set or a permutation.
         PageTranspose xpose;
+        // Cast pages (packed ops only): cast.elem_type != 0 says that the
+        // client holds every page as one-byte e4m3fn codes; block_size stays
+        // the logical bf16 size and the segments speak of client bytes. Never
+        // together with a slice, a tensor set, a permutation or a transpose.
+        PageCast cast;
         const uint8_t* ipc = nullptr;
         size_t ipc_len = 0;
         std::vector<std::pair<std::string_view, uint64_t>> blocks;

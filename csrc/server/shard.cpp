@@ -5,6 +5,7 @@
 #include <cstring>
 
 #include "../core/log.h"
+#include "../gpu/fp8_codec.h"
 #include "completed_prefix.h"
 
 namespace ifs {
@@ -210,6 +211,11 @@ bool Shard::submit_copy(CopyJob&& job) {
                            n_tensors) ||
             job.segs_per_tensor * n_tensors != job.n_segments || slice_is_set(job.slice))
             return false;
+    } else if (cast_is_set(job.cast)) {
+        // A cast job's segments are of CLIENT bytes: cast_legal judges them.
+        if (!cast_legal(job.codec, job.bytes_per_block, job.cast,
+                        PageSegments{job.n_segments, job.segment_stride}))
+            return false;
     } else if (!segments_legal(job.codec, job.bytes_per_block, job.n_segments,
                                job.segment_stride)) {
         return false;
@@ -234,6 +240,9 @@ bool Shard::submit_copy(CopyJob&& job) {
     if (transposed && (sliced || tset || permuted ||
                        !transpose_legal(job.codec, job.bytes_per_block, job.xpose, seg)))
         return false;
+    // So is a cast: next to none of the four.
+    const bool is_cast = cast_is_set(job.cast);
+    if (is_cast && (sliced || tset || permuted || transposed)) return false;
     // A codec with a per-page scale needs one scale slot per block.
     const bool page_scale = page_codec_info(job.codec).page_scale;
     if (page_scale && (!job.scales || job.scales->size() < job.scales_off + n)) return false;
@@ -260,6 +269,7 @@ bool Shard::submit_copy(CopyJob&& job) {
             sub.segs_per_tensor = job.segs_per_tensor;
             sub.perm = job.perm;
             sub.xpose = job.xpose;
+            sub.cast = job.cast;
             sub.scales = job.scales;
             sub.scales_off = job.scales_off + off;
             sub.src.assign(job.src.begin() + static_cast<long>(off),
@@ -365,6 +375,28 @@ bool Shard::submit_copy(CopyJob&& job) {
             if (job.done) job.done(true);
             return true;
         }
+        if (is_cast) {
+            // Element e of the page: a code in the client page, which is
+            // split into segments of client bytes, and bf16 bits in the
+            // stored one; the scalar rules are the kernels' (fp8_codec.h).
+            const bool store = job.dir == PageDir::kStore;
+            const uint64_t elems = job.bytes_per_block / kPageElemBytes;
+            const uint64_t per_seg = elems / seg.n, per_half = elems / job.cast.halves;
+            for (size_t i = 0; i < n; i++) {
+                uint8_t* client = reinterpret_cast<uint8_t*>(store ? job.src[i] : job.dst[i]);
+                uint16_t* pool = reinterpret_cast<uint16_t*>(store ? job.dst[i] : job.src[i]);
+                for (uint64_t e = 0; e < elems; e++) {
+                    uint8_t* c = client + (e / per_seg) * seg.stride_bytes + e % per_seg;
+                    const float sc = job.cast.scale[e / per_half];
+                    if (store)
+                        pool[e] = fp8::cast_code_to_bf16(*c, sc);
+                    else
+                        *c = fp8::cast_bf16_to_code(pool[e], 1.0f / sc);
+                }
+            }
+            if (job.done) job.done(true);
+            return true;
+        }
         const size_t seg_bytes = job.bytes_per_block / seg.n;
         const uint64_t src_step = job.dir == PageDir::kStore ? seg.stride_bytes : seg_bytes;
         const uint64_t dst_step = job.dir == PageDir::kStore ? seg_bytes : seg.stride_bytes;
@@ -380,7 +412,7 @@ bool Shard::submit_copy(CopyJob&& job) {
     bool aligned = job.bytes_per_block % 16 == 0;
     // Segments of a page start at multiples of the stride and of the segment
     // size: both must keep the 16-byte alignment too.
-    if (segmented)
+    if (segmented && !is_cast)
         aligned = aligned && (job.bytes_per_block / seg.n) % 16 == 0 && seg.stride_bytes % 16 == 0;
     // The client descriptors below are offsets inside every tensor: the
     // bases must keep the alignment as well.
@@ -402,6 +434,8 @@ bool Shard::submit_copy(CopyJob&& job) {
     if (!aligned && transforms) return false;
     // Neither have the transpose kernels, for any codec.
     if (!aligned && transposed) return false;
+    // Nor the cast kernels; cast_legal has judged their segments and stride.
+    if (!aligned && is_cast) return false;
 
     // HIP stream enqueues are thread-safe; each job's ops precede its event
     // in stream order regardless of interleaving with other submitters, so
@@ -438,7 +472,7 @@ bool Shard::submit_copy(CopyJob&& job) {
     // (Segmented, sliced and tensor-set jobs always use the pinned-descriptor
     // kernels.)
     if (aligned && n <= 16 && !transforms && !segmented && !sliced && !tset && !permuted &&
-        !transposed) {
+        !transposed && !is_cast) {
         Slot* slot = acquire_slot(sc);
         if (!slot) return false;
         bool ok = gpu::set_device(opt_.device) &&
@@ -531,6 +565,21 @@ bool Shard::submit_copy(CopyJob&& job) {
                                opt_.device, sc.stream, job.codec, job.dir, dsrc, ddst,
                                slot->h_scale, static_cast<int>(take),
                                job.bytes_per_block / kPageElemBytes, aligned, seg, job.xpose);
+            }
+        } else if (is_cast) {
+            if (!transforms) {
+                ok = ok && gpu::launch_copy_blocks_cast(opt_.device, sc.stream, dsrc, ddst,
+                                                        static_cast<int>(take),
+                                                        job.bytes_per_block, aligned, seg,
+                                                        job.dir, job.cast);
+            } else {
+                if (page_scale && job.dir == PageDir::kLoad)
+                    memcpy(slot->h_scale, job.scales->data() + job.scales_off + off,
+                           take * sizeof(float));
+                ok = ok && gpu::launch_transform_blocks_cast(
+                               opt_.device, sc.stream, job.codec, job.dir, dsrc, ddst,
+                               slot->h_scale, static_cast<int>(take),
+                               job.bytes_per_block / kPageElemBytes, aligned, seg, job.cast);
             }
         } else if (!transforms) {
             ok = ok && gpu::launch_copy_blocks(opt_.device, sc.stream, dsrc, ddst,

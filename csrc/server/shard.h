@@ -86,6 +86,14 @@ class Shard {
         // path and carries no slice, tensor set or permutation; on the GPU it
         // needs 16-byte-aligned pointers and stride for every codec.
         PageTranspose xpose;
+        // Cast pages (core/page_codec.h, cast_legal): with cast.elem_type != 0
+        // the CLIENT side holds every page as one-byte e4m3fn codes, and
+        // n_segments / segment_stride speak of CLIENT bytes; bytes_per_block
+        // stays the logical bf16 page. Both directions. Such a job never takes
+        // the inline-argument path and carries no slice, tensor set,
+        // permutation or transpose; on the GPU it needs 16-byte-aligned
+        // pointers for every codec.
+        PageCast cast;
         // Codecs with a per-page scale: block i's scale is
         // (*scales)[scales_off + i], written before done() by kStore and
         // read at submit by kLoad. Fan-out sub-jobs share the vector.

@@ -10,6 +10,7 @@ from .lib import (
     PageSlice,
     PagePermute,
     PageTranspose,
+    PageCast,
     TensorSet,
     DisableTorchCaching,
     ClientConfig,
@@ -39,6 +40,7 @@ __all__ = [
     "PageSlice",
     "PagePermute",
     "PageTranspose",
+    "PageCast",
     "TensorSet",
     "DisableTorchCaching",
     "register_server",

@@ -28,6 +28,7 @@ SOURCES = [
     CSRC / "gpu" / "gpu.hip",
     CSRC / "gpu" / "quant_error.hip",
     CSRC / "gpu" / "transpose.hip",
+    CSRC / "gpu" / "cast.hip",
     CSRC / "fabric" / "verbs_fabric.cpp",
     CSRC / "server" / "shard.cpp",
     CSRC / "server" / "kv_index.cpp",
@@ -44,6 +45,7 @@ _NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 HIP_EXTRA_FLAGS = {
     "quant_error.hip": _NO_PACKED_FP32,
     "transpose.hip": _NO_PACKED_FP32,
+    "cast.hip": _NO_PACKED_FP32,
 }
 
 HEADERS = sorted((CSRC).rglob("*.h")) + [Path(__file__)]

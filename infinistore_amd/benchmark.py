@@ -93,6 +93,15 @@ def parse_args():
                    help="with --pa: what a reader does without transposed pages, "
                         "read whole token-major pages, then permute().contiguous() "
                         "K and V of each buffer with torch (inside the timed read)")
+    p.add_argument("--fp8-cache", action="store_true",
+                   help="cast pages (local-GPU path): the buffers are an fp8 engine's "
+                        "cache, one-byte e4m3fn codes under a K and a V scale, and the "
+                        "store keeps the bf16 page of their values; --block-size is the "
+                        "LOGICAL bf16 page and the rates count logical bytes")
+    p.add_argument("--fp8-cache-baseline", action="store_true",
+                   help="with --fp8-cache: what an fp8 engine does without cast pages, "
+                        "whole bf16 pages through a staging tensor plus a torch "
+                        "scale-and-cast (inside the timed windows), both ways")
     p.add_argument("--verify", action="store_true")
     p.add_argument("--json", action="store_true", help="print a JSON summary")
     p.add_argument("--spawn-server", action="store_true",
@@ -120,6 +129,30 @@ def pa_geometry(args, page_elems, es):
     if args.pa < 1 or args.pa_head < 1 or page_elems % per_token != 0:
         raise SystemExit("--pa needs a page of 2 x T x H x --pa-head elements")
     return lib.PageTranspose(page_elems // per_token, args.pa, args.pa_head, 16 // es)
+
+
+# --fp8-cache: the scales of the K and the V half. Every code's value then
+# lies in [-1, 1], the range --verify's tolerances are written for.
+FP8_CACHE_SCALES = (1.0 / 448.0, 1.0 / 512.0)
+
+
+def _half_scales(device, inverse=False):
+    """[1, 2, 1] float32 factors of a page viewed as [pages, 2, half]; the
+    inverses are 1.0f / scale in float32, as the cast kernels take them."""
+    s = torch.tensor(FP8_CACHE_SCALES, dtype=torch.float32, device=device)
+    return ((1.0 / s) if inverse else s).view(1, 2, 1)
+
+
+def codes_to_bf16(codes, out):
+    """The torch scale-and-cast an fp8 engine needs before a bf16 write."""
+    c = codes.view(torch.float8_e4m3fn).view(-1, 2, out.shape[-1])
+    out.copy_((c.float() * _half_scales(codes.device)).to(torch.bfloat16))
+
+
+def bf16_to_codes(pages, out):
+    """... and after a bf16 read: the composition the cast kernels compute."""
+    y = torch.clamp(pages.float() * _half_scales(pages.device, inverse=True), -448.0, 448.0)
+    out.view(torch.float8_e4m3fn).view(pages.shape).copy_(y.to(torch.float8_e4m3fn))
 
 
 def slice_geometry(args):
@@ -167,7 +200,7 @@ def make_buffers(args, conn, local, device):
     n_blocks = total_bytes // block_bytes
     per_step = max(1, n_blocks // args.steps)
     dt = torch.bfloat16 if args.quant else torch.float32
-    es = 2 if args.quant else 4
+    es = 2 if args.quant or args.fp8_cache else 4
 
     cap = (1 << 30) + (1 << 28)  # 1.25 GiB
     n_sub = max(1, -(-total_bytes // cap))
@@ -180,6 +213,11 @@ def make_buffers(args, conn, local, device):
     for t in range(n_sub):
         nb = min(blocks_per_sub, n_blocks - t * blocks_per_sub)
         elems = nb * block_bytes // es
+        if args.fp8_cache:  # every e4m3fn code but the two NaNs, one byte an element
+            c = torch.randint(0, 256, (elems,), dtype=torch.uint8, device=device)
+            srcs.append(torch.where((c & 0x7F) == 0x7F, c ^ 1, c))
+            dsts.append(torch.zeros(elems, dtype=torch.uint8, device=dst_dev))
+            continue
         srcs.append(torch.rand(elems, dtype=dt, device=device))
         dsts.append(torch.zeros(elems, dtype=dt, device=dst_dev))
         if not local:
@@ -278,7 +316,7 @@ def run_once(args, conn, local, device, bufs=None):
     block_bytes = args.block_size << 10
     total_bytes = args.size << 20
     n_blocks = total_bytes // block_bytes
-    es = 2 if args.quant else 4
+    es = 2 if args.quant or args.fp8_cache else 4
     page_elems = block_bytes // es
 
     srcs, dsts, blocks_per_sub = (bufs if bufs is not None
@@ -322,8 +360,19 @@ def run_once(args, conn, local, device, bufs=None):
         pa_outs = [torch.zeros_like(d) for d in dsts]
         torch.cuda.synchronize()
 
+    # --fp8-cache: the buffers hold e4m3fn codes; the baseline moves bf16 pages
+    # through staging tensors, allocated outside the timed windows.
+    cast = lib.PageCast(FP8_CACHE_SCALES) if local and args.fp8_cache else None
+    stages = None
+    if cast and args.fp8_cache_baseline:
+        stages = [torch.zeros(d.numel() // page_elems, 2, page_elems // 2, dtype=torch.bfloat16,
+                              device=d.device) for d in dsts]
+        torch.cuda.synchronize()
+
     def geom(t, permuted=True):  # geometry arguments for sub-tensor t
         g = {}
+        if cast and not stages:
+            g["page_cast"] = cast
         if nseg != 1:  # [N, n_pages, page/N]
             g.update(segments=nseg, segment_stride=t.numel() // nseg)
         if perm and permuted:
@@ -339,8 +388,15 @@ def run_once(args, conn, local, device, bufs=None):
         hi = min(s0 + per_step, n_blocks)
         t_idx, _ = sub_of(s0)
         pairs = [(keys[i], sub_of(i)[1]) for i in range(s0, hi)]
-        if local:
-            if args.quant or nseg > 1 or perm or xpose:
+        if local and stages:
+            # the pass an fp8 engine needs today before it can store bf16 pages
+            p0, p1 = pairs[0][1] // page_elems, pairs[-1][1] // page_elems + 1
+            codes_to_bf16(srcs[t_idx][p0 * page_elems:p1 * page_elems], stages[t_idx][p0:p1])
+            torch.cuda.synchronize()
+            conn.write_pages(stages[t_idx].view(-1), [p[0] for p in pairs],
+                             [p[1] for p in pairs], page_elems, quant=args.quant)
+        elif local:
+            if args.quant or nseg > 1 or perm or xpose or cast:
                 conn.write_pages(srcs[t_idx], [p[0] for p in pairs],
                                  [p[1] for p in pairs], page_elems,
                                  quant=args.quant, **geom(srcs[t_idx]))
@@ -380,11 +436,17 @@ def run_once(args, conn, local, device, bufs=None):
                                                          page_slice=page_slice))
                     continue
                 tickets.append(conn.read_pages_async(
-                    dsts[t_idx], ks, offs, page_elems,
+                    stages[t_idx].view(-1) if stages else dsts[t_idx], ks, offs, page_elems,
                     **geom(dsts[t_idx],
                            permuted=not (args.hnd_baseline or args.pa_baseline))))
         for tk in tickets:
             conn.wait_read(tk)
+        if stages:
+            # the second pass an fp8 engine needs today: bf16 pages landed in
+            # the staging tensors, its cache wants codes
+            for st, d in zip(stages, dsts):
+                bf16_to_codes(st, d)
+            torch.cuda.synchronize()
         if perm and args.hnd_baseline:
             # the second pass a reader needs today: token-major pages landed
             # in the bounce buffers (dsts), the engine wants them head-major
@@ -428,6 +490,21 @@ def run_once(args, conn, local, device, bufs=None):
         for a, o in zip(srcs, outs):
             want = a.view(-1, rows, n_heads, head)[:, :, h0:h1].reshape(-1)
             assert _close(want.cpu(), o.cpu(), args.quant), "verification failed (slice)"
+    elif args.verify and cast:
+        # plain: the codes come back (every non-NaN code survives store -> bf16
+        # -> load under one scale). Under a codec: the values, within the
+        # codec's error plus half an e4m3 step of the re-encoding (2^-4 of a
+        # value of at most 1).
+        for a, b in zip(srcs, dsts):
+            if args.quant is None:
+                assert _close(a.cpu(), b.cpu(), None), "verification failed (fp8 cache)"
+                continue
+            va, vb = (torch.empty(t.numel() // page_elems, 2, page_elems // 2,
+                                  dtype=torch.bfloat16, device=t.device) for t in (a, b))
+            codes_to_bf16(a, va)
+            codes_to_bf16(b, vb)
+            assert _close(va.cpu(), vb.cpu(), args.quant, extra=2.0 ** -4), \
+                "verification failed (fp8 cache)"
     elif args.verify:
         for a, b in zip(srcs, hnd_outs or pa_outs or dsts):
             assert _close(a.cpu(), b.cpu(), args.quant), "verification failed"
@@ -452,14 +529,14 @@ def run_once(args, conn, local, device, bufs=None):
 _QUANT_TOL = {"fp8": 2.0 ** -4, "mxfp4": 0.25}
 
 
-def _close(a, b, quant):
+def _close(a, b, quant, extra=0.0):
     """--verify's comparison: exact for plain pages, within the codec's
     error for compressed ones (the harness data is uniform in [0, 1)).
     Says where the first difference is."""
     if quant is None:
         bad = a != b
     else:
-        bad = ~((a.float() - b.float()).abs() <= _QUANT_TOL[quant])
+        bad = ~((a.float() - b.float()).abs() <= _QUANT_TOL[quant] + extra)
     n_bad = int(bad.sum())
     if n_bad:
         first = int(bad.reshape(-1).nonzero()[0])
@@ -616,6 +693,14 @@ def main():
                     or args.fused_layers or args.hnd):
         raise SystemExit("--pa needs --local-gpu and no --segments, --slice, "
                          "--fused-layers or --hnd")
+    if args.fp8_cache_baseline and not args.fp8_cache:
+        raise SystemExit("--fp8-cache-baseline needs --fp8-cache")
+    if args.fp8_cache and (not args.local_gpu or args.segments != 1 or args.slice
+                           or args.fused_layers or args.hnd or args.pa or args.clients > 1
+                           or (args.block_size << 10) % 128):
+        raise SystemExit("--fp8-cache needs --local-gpu, one client, a page of whole "
+                         "64-element halves and no --segments, --slice, --fused-layers, "
+                         "--hnd or --pa")
     if args.slice:
         if not args.local_gpu or args.segments != 1:
             raise SystemExit("--slice needs --local-gpu and --segments 1")

@@ -89,7 +89,8 @@ class PagedKVConnector:
     # -- prefill side ---------------------------------------------------------
     def save_layer(self, layer: int, kv: torch.Tensor, page_keys: List[str],
                    page_offsets, page_elems: int, segments: int = 1,
-                   segment_stride: int = 0, page_permute=None, page_transpose=None):
+                   segment_stride: int = 0, page_permute=None, page_transpose=None,
+                   page_cast=None):
         """Store this layer's pages of `kv` (offsets in elements). Call per
         layer as prefill produces them; uploads overlap later layers'
         compute (writes are async until sync()). segments / segment_stride:
@@ -97,14 +98,18 @@ class PagedKVConnector:
         only, ValueError on the fabric path). page_permute: `kv` holds each
         page with two piece axes exchanged (PagePermute; local path only).
         page_transpose: `kv` holds each page as a paged-attention cache block
-        (PageTranspose; local path only)."""
+        (PageTranspose; local path only). page_cast: `kv` is an fp8 engine's
+        cache, e4m3fn codes under a scale per half (PageCast; local path
+        only)."""
         keys = [self._key(layer, k) for k in page_keys]
+        if page_cast is not None and not self.local:
+            raise ValueError("cast pages use the local GPU path")
         if self.local:
             self.conn.write_pages(kv, keys, page_offsets, page_elems,
                                   quant=self.quant, segments=segments,
                                   segment_stride=segment_stride,
                                   page_permute=page_permute,
-                                  page_transpose=page_transpose)
+                                  page_transpose=page_transpose, page_cast=page_cast)
         elif page_permute is not None:
             raise ValueError("permuted pages use the local GPU path")
         elif page_transpose is not None:
@@ -124,10 +129,11 @@ class PagedKVConnector:
     def load_layer(self, layer: int, kv_out: torch.Tensor, page_keys: List[str],
                    page_offsets, page_elems: int, segments: int = 1,
                    segment_stride: int = 0, page_slice=None, page_permute=None,
-                   page_transpose=None) -> bool:
+                   page_transpose=None, page_cast=None) -> bool:
         """Gather this layer's cached pages into the engine's KV tensor.
         Returns False if any page is missing (caller falls back to compute).
-        segments / segment_stride / page_slice / page_permute / page_transpose: as in
+        segments / segment_stride / page_slice / page_permute / page_transpose /
+        page_cast: as in
         InfinityConnection.read_pages (page_elems is then the sliced page); a
         refused geometry raises ValueError."""
         keys = [self._key(layer, k) for k in page_keys]
@@ -135,6 +141,8 @@ class PagedKVConnector:
         self.conn._permute_arg(page_permute, page_elems, segments, None, page_slice)
         if page_transpose is not None and not self.local:
             raise ValueError("transposed pages use the local GPU path")
+        if page_cast is not None and not self.local:
+            raise ValueError("cast pages use the local GPU path")
         if segments != 1 and not self.local:
             raise ValueError("segmented pages use the local GPU path")
         if page_slice is not None and not self.local:
@@ -148,7 +156,7 @@ class PagedKVConnector:
                                      segment_stride=segment_stride,
                                      page_slice=page_slice,
                                      page_permute=page_permute,
-                                     page_transpose=page_transpose)
+                                     page_transpose=page_transpose, page_cast=page_cast)
             else:
                 self._ensure_mr(kv_out)
                 blocks = [(k, int(o)) for k, o in zip(keys, page_offsets)]
@@ -156,25 +164,28 @@ class PagedKVConnector:
             self.conn.sync()
             return True
         except ValueError:
-            if page_transpose is None:
+            if page_transpose is None and page_cast is None:
                 return False
-            raise  # a transposed read's arguments are checked by read_pages alone
+            raise  # a transposed or cast read's arguments are checked by read_pages alone
         except Exception:
             return False
 
     def load_layer_async(self, layer: int, kv_out: torch.Tensor,
                          page_keys: List[str], page_offsets, page_elems: int,
                          segments: int = 1, segment_stride: int = 0,
-                         page_slice=None, page_permute=None, page_transpose=None):
+                         page_slice=None, page_permute=None, page_transpose=None,
+                         page_cast=None):
         """Ticketed prefetch (local path): push the gather and return a
         ticket; call wait_load(ticket) before touching kv_out. Lets decode
         overlap the next request's KV fetch with current compute. Returns
         None if any page was missing or the path is unavailable (caller
-        falls back to load_layer / recompute). page_slice, page_permute and
-        page_transpose as in load_layer."""
+        falls back to load_layer / recompute). page_slice, page_permute,
+        page_transpose and page_cast as in load_layer."""
         self.conn._permute_arg(page_permute, page_elems, segments, None, page_slice)
         if page_transpose is not None and not self.local:
             raise ValueError("transposed pages use the local GPU path")
+        if page_cast is not None and not self.local:
+            raise ValueError("cast pages use the local GPU path")
         if not self.local:
             if segments != 1:
                 raise ValueError("segmented pages use the local GPU path")
@@ -190,9 +201,10 @@ class PagedKVConnector:
                                               segment_stride=segment_stride,
                                               page_slice=page_slice,
                                               page_permute=page_permute,
-                                              page_transpose=page_transpose)
+                                              page_transpose=page_transpose,
+                                              page_cast=page_cast)
         except ValueError:
-            if page_transpose is None:
+            if page_transpose is None and page_cast is None:
                 return None
             raise  # as in load_layer
         except Exception:

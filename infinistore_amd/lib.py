@@ -305,6 +305,35 @@ class PageTranspose(NamedTuple):
     halves: int = 2
 
 
+class PageCast:
+    """Client-side element type of a page (docs/design.md, "cast pages"): the
+    tensor (torch.float8_e4m3fn or uint8) holds each page as one-byte OCP
+    e4m3fn codes, element value = code value * scales[h] with h the half of
+    the page (K, then V) the element lies in, vLLM's kv_cache_dtype="fp8"
+    convention with k_scale and v_scale. The store keeps, and every other
+    reader sees, the bf16 page of the dequantized values. scales: one or two
+    finite, positive, normal float32 values; halves defaults to their number,
+    and PageCast([s], halves=2) applies one scale to both halves."""
+
+    __slots__ = ("scales", "halves")
+
+    def __init__(self, scales, halves: Optional[int] = None):
+        scales = [scales] if isinstance(scales, (int, float)) else list(scales)
+        if len(scales) not in (1, 2):
+            raise ValueError("PageCast takes one or two scales")
+        self.scales = tuple(float(np.float32(x)) for x in scales)
+        self.halves = len(scales) if halves is None else int(halves)
+        if self.halves not in (1, 2) or self.halves < len(scales):
+            raise ValueError("PageCast.halves is 1 or 2, and at least the number of scales")
+
+    def wire(self):
+        """What the native calls take: (elem_type, halves, scale_k, scale_v)."""
+        return (1, self.halves, self.scales[0], self.scales[-1])
+
+    def __repr__(self):
+        return f"PageCast(scales={self.scales}, halves={self.halves})"
+
+
 class TensorSet:
     """A registered tensor set (InfinityConnection.register_tensor_set): the
     server-side id and the tensors, which it keeps alive."""
@@ -569,6 +598,68 @@ class InfinityConnection:
                              "segment stride")
         return geo
 
+    CAST_DTYPES = (torch.float8_e4m3fn, torch.uint8)
+
+    def _cast_arg(self, page_cast, cache, offsets, page_size: int, segments: int,
+                  segment_stride: int, quant=None, page_slice=None, tensor_set=None,
+                  page_permute=None, page_transpose=None):
+        """Refuse (ValueError) a cast request the store cannot serve, before
+        anything is sent; the geometry rule is the native cast_legal. Returns
+        what the native calls take: (1, halves, scale_k, scale_v)."""
+        if (page_slice is not None or tensor_set is not None or page_permute is not None
+                or page_transpose is not None):
+            raise ValueError("page_cast cannot be combined with page_slice, tensor_set, "
+                             "page_permute or page_transpose")
+        if not self.local_connected:
+            raise ValueError("cast pages use the local GPU path")
+        if not isinstance(page_cast, PageCast):
+            raise ValueError("page_cast must be a PageCast")
+        if cache.dtype not in self.CAST_DTYPES:
+            raise ValueError("page_cast needs a torch.float8_e4m3fn or uint8 cache")
+        if quant is not None and quant not in self.QUANT_MODES:
+            raise ValueError(f"unsupported quant mode {quant!r}")
+        if not 0 < page_size < 1 << 60 or not 0 < segments < 1 << 32 or segment_stride < 0:
+            raise ValueError("page_size and segments must be positive")
+        if not _native._dbg_cast_legal(self.QUANT_CODECS[quant], page_size * 2, page_cast.wire(),
+                                       segments, segment_stride):
+            raise ValueError(
+                "illegal page cast: scales are finite, positive, normal float32 values; "
+                "page_size / halves is a multiple of 8 elements (32 with mxfp4); segments "
+                "are equal parts of a multiple of 8 (32) elements, at most "
+                f"{self.MAX_PAGE_SEGMENTS}, with a segment_stride of at least one segment "
+                "and a multiple of 16")
+        offs = np.asarray(offsets, dtype=np.uint64)
+        if cache.data_ptr() % 16 != 0 or (offs % np.uint64(16)).any():
+            raise ValueError("cast pages need a 16-byte-aligned cache and page offsets")
+        if len(offs) and (int(offs.max()) + (segments - 1) * segment_stride
+                          + page_size // segments > cache.numel()):
+            raise ValueError("a cast page extends outside the tensor")
+        return page_cast.wire()
+
+    def _rw_cast(self, op, cache, keys, offsets, page_size, segments, segment_stride, cast,
+                 sync=False, flags=0, ticketed=False):
+        """One cast request: element size 1, block size the LOGICAL bf16 bytes,
+        offsets and stride in client bytes. Returns the ticket (0 unless
+        ticketed)."""
+        offs = np.asarray(offsets, dtype=np.uint64)
+        args = (1, page_size * 2, cache.data_ptr(), _remap_device_id(cache))
+        ticket = 0
+        if ticketed:
+            if not isinstance(keys, (bytes, bytearray, memoryview)):
+                keys = self.pack_keys(keys)
+            ret, ticket = self.conn.rw_local_blob_async(
+                op, keys, offs, *args, segments, segment_stride, None, None, None, cast)
+        elif isinstance(keys, (bytes, bytearray, memoryview)):
+            ret = self.conn.rw_local_blob(op, keys, offs, *args, sync, flags, segments,
+                                          segment_stride, None, None, None, cast)
+        else:
+            ret = self.conn.rw_local_keys(op, keys, offs, *args, sync, flags, segments,
+                                          segment_stride, None, None, None, cast)
+        if ret < 0:
+            what = "write to" if op == self.OP_W else "read from"
+            raise Exception(f"Failed to {what} infinistore, ret = {ret}")
+        return ticket
+
     @staticmethod
     def _slice_arg(page_slice):
         """The native (n_pieces, page, offset, piece, stride) tuple, or None."""
@@ -674,7 +765,8 @@ class InfinityConnection:
                     sync: bool = False, quant: Optional[str] = None,
                     segments: Optional[int] = None, segment_stride: int = 0,
                     tensor_set=None, page_permute: Optional[PagePermute] = None,
-                    page_transpose: Optional[PageTranspose] = None, **unsupported):
+                    page_transpose: Optional[PageTranspose] = None,
+                    page_cast: Optional[PageCast] = None, **unsupported):
         """sync=True completes the write in ONE round trip (the response is
         sent when the copy finishes); sync=False (default) returns after the
         server accepts, so uploads overlap compute — call sync() later.
@@ -734,6 +826,15 @@ class InfinityConnection:
         and stride must be 16-byte aligned; an illegal geometry is a
         ValueError before anything is sent.
 
+        page_cast=PageCast([k_scale, v_scale]): `cache` is an fp8 engine's
+        cache (torch.float8_e4m3fn or uint8, see PageCast); page_size, offsets
+        and segment_stride stay in elements, one byte each. The stored page is
+        what a bf16 writer holding code * scale would have stored, under every
+        quant, so bf16 engines read it as usual. Works with segments; local
+        path only, not with tensor_set, page_permute or page_transpose; cache
+        and offsets must be 16-byte aligned; anything the server would refuse
+        is a ValueError before anything is sent.
+
         Slices are read-only: write_pages has no page_slice parameter, and
         passing one is a ValueError."""
         if "page_slice" in unsupported:
@@ -748,6 +849,9 @@ class InfinityConnection:
             if page_transpose is not None:
                 raise ValueError("page_transpose cannot be combined with page_slice, "
                                  "tensor_set or page_permute")
+            if page_cast is not None:
+                raise ValueError("page_cast cannot be combined with page_slice, tensor_set, "
+                                 "page_permute or page_transpose")
             if cache is not None:
                 raise ValueError("pass either cache or tensor_set")
             if quant is not None and quant not in self.QUANT_MODES:
@@ -764,6 +868,12 @@ class InfinityConnection:
             return 0
         segments = 1 if segments is None else segments
         self._verify(cache)
+        if page_cast is not None:
+            cast = self._cast_arg(page_cast, cache, offsets, page_size, segments, segment_stride,
+                                  quant, None, None, page_permute, page_transpose)
+            self._rw_cast(self.OP_W, cache, keys, offsets, page_size, segments, segment_stride,
+                          cast, sync, self.QUANT_MODES[quant][0] if quant else 0)
+            return 0
         if segments != 1 and not self.local_connected:
             raise ValueError("segmented pages use the local GPU path")
         if page_permute is not None and not self.local_connected:
@@ -813,7 +923,8 @@ class InfinityConnection:
                    segments: Optional[int] = None, segment_stride: int = 0,
                    page_slice: Optional[PageSlice] = None, tensor_set=None,
                    page_permute: Optional[PagePermute] = None,
-                   page_transpose: Optional[PageTranspose] = None):
+                   page_transpose: Optional[PageTranspose] = None,
+                   page_cast: Optional[PageCast] = None):
         """segments / segment_stride: scatter each page into that many equal
         pieces of `cache` (see write_pages), however the page was written.
         Local path only.
@@ -840,7 +951,23 @@ class InfinityConnection:
         page_transpose: deliver each page as a paged-attention cache block
         (see write_pages), however it was written. page_size must be the
         written one. Not together with page_slice, tensor_set or
-        page_permute."""
+        page_permute.
+
+        page_cast: deliver each page as e4m3fn codes under the given scales
+        (see write_pages), however it was written: the stored element is
+        decoded to bf16 as for a bf16 reader, then divided by its half's scale
+        and rounded to e4m3fn (saturating at +-448). page_size must be the
+        written one. Not together with page_slice, tensor_set, page_permute
+        or page_transpose."""
+        if page_cast is not None:
+            segments = 1 if segments is None else segments
+            if tensor_set is None:
+                self._verify(cache)
+            cast = self._cast_arg(page_cast, cache, offsets, page_size, segments, segment_stride,
+                                  None, page_slice, tensor_set, page_permute, page_transpose)
+            self._rw_cast(self.OP_R, cache, keys, offsets, page_size, segments, segment_stride,
+                          cast)
+            return
         if tensor_set is not None:
             self._permute_arg(page_permute, page_size, 1, None, page_slice, tensor_set)
             self._transpose_arg(page_transpose, None, None, page_size, 1, 0, None, page_slice,
@@ -906,14 +1033,23 @@ class InfinityConnection:
                          segments: Optional[int] = None, segment_stride: int = 0,
                          page_slice: Optional[PageSlice] = None, tensor_set=None,
                          page_permute: Optional[PagePermute] = None,
-                         page_transpose: Optional[PageTranspose] = None):
+                         page_transpose: Optional[PageTranspose] = None,
+                         page_cast: Optional[PageCast] = None):
         """Ticketed read (local path, shm ring): pushes the request and
         returns a ticket; call wait_read(ticket) before using the data. Lets
         an engine overlap its own work (or further requests) with the copy —
         e.g. prefetching the next sequence's KV pages while decoding. Falls
         back to a blocking read (ticket 0) when the ring is unavailable.
         segments / segment_stride / page_slice / tensor_set / page_permute /
-        page_transpose as in read_pages."""
+        page_transpose / page_cast as in read_pages."""
+        if page_cast is not None:
+            segments = 1 if segments is None else segments
+            if tensor_set is None:
+                self._verify(cache)
+            cast = self._cast_arg(page_cast, cache, offsets, page_size, segments, segment_stride,
+                                  None, page_slice, tensor_set, page_permute, page_transpose)
+            return self._rw_cast(self.OP_R, cache, keys, offsets, page_size, segments,
+                                 segment_stride, cast, ticketed=True)
         if tensor_set is not None:
             self._permute_arg(page_permute, page_size, 1, None, page_slice, tensor_set)
             self._transpose_arg(page_transpose, None, None, page_size, 1, 0, None, page_slice,

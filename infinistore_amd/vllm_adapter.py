@@ -44,7 +44,7 @@ from typing import Dict, List, Optional, Sequence
 import torch
 
 from .kv_connector import PagedKVConnector, token_page_hashes
-from .lib import PagePermute, PageSlice, PageTranspose
+from .lib import PageCast, PagePermute, PageSlice, PageTranspose
 
 
 class InfiniStoreKVAdapter:
@@ -110,11 +110,24 @@ class InfiniStoreKVAdapter:
             page (docs/design.md, "transposed pages"); ``kv_layout="kv_major"``
             is vLLM's one ``[2, num_blocks, ...]`` allocation. The same keys,
             quants and restrictions as for "hnd".
+        cache_dtype, k_scale, v_scale: "auto" (default): the cache tensors
+            hold what the store treats as the page. "fp8_e4m3": vLLM's
+            ``kv_cache_dtype="fp8"`` cache, one-byte e4m3fn codes
+            (``torch.float8_e4m3fn`` or ``uint8`` tensors) whose values are
+            ``code * k_scale`` in the K half and ``code * v_scale`` in the V
+            half (both required). Every page then travels as a cast page
+            (docs/design.md, "cast pages") and is stored as a bf16 engine
+            holding the dequantized values stores it, so fp8 and bf16 engines
+            share keys. Works with ``cache_layout="nhd"``, both kv_layout
+            values and every quant; needs the local path; with another
+            cache_layout, head_range or layer_pages="fused" it raises
+            ValueError.
     """
 
     KV_LAYOUTS = ("block_major", "kv_major")
     CACHE_LAYOUTS = ("nhd", "hnd", "pa")
     LAYER_PAGES = ("per_layer", "fused")
+    CACHE_DTYPES = ("auto", "fp8_e4m3")
 
     def __init__(self, host: str, port: int, model_tag: str, n_layers: int,
                  block_tokens: int, page_elems: int, local: bool = True,
@@ -122,7 +135,25 @@ class InfiniStoreKVAdapter:
                  stored_kv_heads: Optional[int] = None,
                  head_range: Optional[Sequence[int]] = None,
                  head_dim: Optional[int] = None, layer_pages: str = "per_layer",
-                 cache_layout: str = "nhd", cache_kv_heads: Optional[int] = None):
+                 cache_layout: str = "nhd", cache_kv_heads: Optional[int] = None,
+                 cache_dtype: str = "auto", k_scale: Optional[float] = None,
+                 v_scale: Optional[float] = None):
+        if cache_dtype not in self.CACHE_DTYPES:
+            raise ValueError(f"cache_dtype must be one of {self.CACHE_DTYPES}")
+        self._page_cast = None
+        if cache_dtype == "fp8_e4m3":
+            if k_scale is None or v_scale is None:
+                raise ValueError('cache_dtype="fp8_e4m3" needs k_scale and v_scale')
+            if not local:
+                raise ValueError('cache_dtype="fp8_e4m3" uses cast pages, which need the '
+                                 "local GPU path")
+            if cache_layout != "nhd" or head_range is not None or layer_pages == "fused":
+                raise ValueError('cache_dtype="fp8_e4m3" needs cache_layout="nhd" and cannot be '
+                                 'combined with head_range or layer_pages="fused": a cast page '
+                                 "takes no permutation, transpose, slice or tensor set")
+            self._page_cast = PageCast([k_scale, v_scale])
+        elif k_scale is not None or v_scale is not None:
+            raise ValueError('k_scale and v_scale go with cache_dtype="fp8_e4m3"')
         if layer_pages not in self.LAYER_PAGES:
             raise ValueError(f"layer_pages must be one of {self.LAYER_PAGES}")
         if cache_layout not in self.CACHE_LAYOUTS:
@@ -364,6 +395,8 @@ class InfiniStoreKVAdapter:
             geo["page_permute"] = self._page_permute
         if self._pa is not None:
             geo["page_transpose"] = PageTranspose(*self._pa, 16 // kv_cache.element_size())
+        if self._page_cast is not None:
+            geo["page_cast"] = self._page_cast
         if self.kv_layout == "kv_major":
             geo.update(segments=2, segment_stride=kv_cache.numel() // 2)
         return geo
