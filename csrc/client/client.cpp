@@ -404,7 +404,8 @@ int ClientConn::rw_local_packed(char op, const char* keys_blob, size_t blob_len,
                                 const PackedLocalTensorExt* tset,
                                 const PackedLocalPermExt* perm,
                                 const PackedLocalXposeExt* xpose,
-                                const PackedLocalCastExt* cast) {
+                                const PackedLocalCastExt* cast,
+                                const PackedLocalRotExt* rot, const float* rot_table) {
     if (out_ticket) *out_ticket = 0;  // 0 = completed synchronously
     if (!connected_) return -1;
     if (perm && perm->rows != 0 && ((slice && slice->n_pieces != 0) || tset))
@@ -416,6 +417,11 @@ int ClientConn::rw_local_packed(char op, const char* keys_blob, size_t blob_len,
         ((slice && slice->n_pieces != 0) || tset || (perm && perm->rows != 0) ||
          (xpose && xpose->tokens != 0)))
         return -INVALID_REQ;  // not together
+    if (rot && rot->style != 0 &&
+        (op != 'R' || !rot_table || (slice && slice->n_pieces != 0) || tset ||
+         (perm && perm->rows != 0) || (xpose && xpose->tokens != 0) ||
+         (cast && cast->elem_type != 0)))
+        return -INVALID_REQ;  // read-only, and not together
     if (slice && slice->n_pieces != 0 && op != 'R') return -INVALID_REQ;  // read-only
     if (slice && slice->n_pieces != 0 && tset) return -INVALID_REQ;  // not together
     if (!gpu::available()) {
@@ -471,7 +477,7 @@ int ClientConn::rw_local_packed(char op, const char* keys_blob, size_t blob_len,
 
     std::vector<uint8_t> body =
         build_packed_local(h, n_segments, segment_stride, offsets, keys_blob, blob_len, slice,
-                           tset, perm, xpose, cast);
+                           tset, perm, xpose, cast, rot, rot_table);
 
     char wire_op = (op == 'W') ? OP_W_FAST : OP_R_FAST;
     static const bool dbg = getenv("IFS_CLIENT_DEBUG") != nullptr;

@@ -79,7 +79,14 @@ class ClientConn {
                         const PackedLocalTensorExt* tset = nullptr,
                         const PackedLocalPermExt* perm = nullptr,
                         const PackedLocalXposeExt* xpose = nullptr,
-                        const PackedLocalCastExt* cast = nullptr);
+                        const PackedLocalCastExt* cast = nullptr,
+                        const PackedLocalRotExt* rot = nullptr,
+                        const float* rot_table = nullptr);
+    // rot (null or style == 0: not rotated) with rot_table, rot->rot_dim
+    // (cos, sin) floats: a READ turns the K half of every bf16 page while it
+    // loads (rotated reads, core/page_codec.h). On a write, or with a slice, a
+    // tensor set, a permutation, a transpose or a cast as well, it returns
+    // -INVALID_REQ without sending anything.
     // cast (null or elem_type == 0: not cast): the tensor holds every page as
     // one-byte e4m3fn codes (cast pages, core/page_codec.h); block_size stays
     // the logical bf16 size, offsets and the segment stride are client bytes.

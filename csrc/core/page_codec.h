@@ -393,4 +393,78 @@ inline PageCast cast_from_wire(const PackedLocalCastExt& e) {
     return {e.elem_type, e.halves, {e.scale[0], e.scale[1]}};
 }
 
+// Rotated reads (docs/design.md, "rotated reads"): a READ may shift the rotary
+// position embedding of the keys it loads. The page is [halves, T, heads,
+// head_dim] bf16, T implied by the page size; half 0 (K) is rotated, half 1
+// (V) is copied. With P = rot_dim / 2 pairs per head and (cos_i, sin_i) =
+// table[2i], table[2i + 1], pair i of every (token, head) row is channels
+// (i, i + P) under style 1 (NeoX halves) and (2i, 2i + 1) under style 2 (GPT-J
+// interleaved); channels at or above rot_dim are copied (partial rotary). For
+// a pair (a, b) of decoded bf16 values, in float32,
+//     out_a = fma(a, cos, -(b * sin)),  out_b = fma(b, cos, a * sin),
+// each rounded to bf16 (gpu/rotate_math.h). The bound is a condition, not a
+// tuning value: the table is 1 KiB, as the tensor-set table is.
+constexpr uint32_t kMaxRotatePairs = 128;
+constexpr uint32_t kRotateNeox = 1, kRotateGptj = 2;
+
+// Read-side rotation of a request's pages; style == 0 (the default) is "not
+// rotated". table points at rot_dim floats in host memory that outlive the
+// struct's use; Shard::CopyJob keeps its own copy.
+struct PageRotate {
+    uint32_t style = 0;
+    uint32_t halves = 0;
+    uint32_t heads = 0, head_dim = 0, rot_dim = 0;  // elements
+    const float* table = nullptr;
+};
+
+inline bool rotate_is_set(const PageRotate& r) { return r.style != 0; }
+
+// The one predicate for a rotated read (wire parser, server, shard, launcher,
+// bindings, Python client). The kernels move 8-element lane units and, under
+// mxfp4, decode whole 32-element groups: a unit never holds both rotated and
+// copied channels, never half a pair and never parts of two heads, so
+// head_dim is a multiple of 8 under both styles. A client segment holds whole
+// (token, head) rows, and its stride keeps every unit 16-byte aligned under
+// every codec, because there is no byte path. Every table entry is finite
+// (judged on its bits).
+inline bool rotate_legal(PageCodec c, size_t page_bytes, const PageRotate& r,
+                         const PageSegments& seg = {}) {
+    if (r.style != kRotateNeox && r.style != kRotateGptj) return false;
+    if (r.halves != 1 && r.halves != 2) return false;
+    if (r.heads < 1 || r.head_dim < 1 || r.rot_dim < 1 || r.rot_dim > r.head_dim) return false;
+    if (r.rot_dim % 2 != 0) return false;
+    const uint32_t pairs = r.rot_dim / 2;
+    if (pairs > kMaxRotatePairs) return false;
+    if (r.head_dim % 8 != 0) return false;
+    if (r.style == kRotateNeox ? pairs % 8 != 0 : r.rot_dim % 8 != 0) return false;
+    if (c == PageCodec::kMxfp4) {
+        if (r.head_dim % 32 != 0 || r.rot_dim % 32 != 0) return false;
+        if (r.style == kRotateNeox && pairs % 32 != 0) return false;
+    }
+    // 128-bit products: three 32-bit values off the wire must not wrap.
+    using u128 = unsigned __int128;
+    const u128 row = static_cast<u128>(r.head_dim) * kPageElemBytes;
+    const u128 token = row * r.halves * r.heads;
+    if (page_bytes == 0 || static_cast<u128>(page_bytes) % token != 0) return false;
+    if (!page_legal(c, page_bytes)) return false;
+    if (!segments_legal(c, page_bytes, seg.n, seg.stride_bytes)) return false;
+    if (seg.n > 1) {
+        if (static_cast<u128>(page_bytes / seg.n) % row != 0) return false;
+        if (seg.stride_bytes % 16 != 0) return false;
+    }
+    if (!r.table) return false;
+    for (uint32_t i = 0; i < r.rot_dim; i++)
+        if ((__builtin_bit_cast(uint32_t, r.table[i]) & 0x7f800000u) == 0x7f800000u) return false;
+    return true;
+}
+
+// The geometry as the wire extension carries it, and back; the table travels
+// behind the extension.
+inline PackedLocalRotExt rotate_to_wire(const PageRotate& r) {
+    return {r.style, r.halves, r.heads, r.head_dim, r.rot_dim, 0};
+}
+inline PageRotate rotate_from_wire(const PackedLocalRotExt& e, const float* table) {
+    return {e.style, e.halves, e.heads, e.head_dim, e.rot_dim, table};
+}
+
 }  // namespace ifs

@@ -165,7 +165,8 @@ std::vector<uint8_t> build_packed_local(PackedLocalHdr h, uint32_t n_segments,
                                         const PackedLocalTensorExt* tset,
                                         const PackedLocalPermExt* perm,
                                         const PackedLocalXposeExt* xpose,
-                                        const PackedLocalCastExt* cast) {
+                                        const PackedLocalCastExt* cast,
+                                        const PackedLocalRotExt* rot, const float* rot_table) {
     const size_t n = h.n_blocks;
     const bool seg = n_segments != 1;
     const bool sliced = slice && slice->n_pieces != 0;
@@ -183,7 +184,11 @@ std::vector<uint8_t> build_packed_local(PackedLocalHdr h, uint32_t n_segments,
     const size_t xpose_end = perm_end + (transposed ? sizeof(PackedLocalXposeExt) : 0);
     const bool is_cast = cast && cast->elem_type != 0;
     if (is_cast) h.flags |= kLocalFlagCast;
-    const size_t ext = xpose_end + (is_cast ? sizeof(PackedLocalCastExt) : 0);
+    const size_t cast_end = xpose_end + (is_cast ? sizeof(PackedLocalCastExt) : 0);
+    const bool rotated = rot && rot->style != 0;
+    if (rotated) h.flags |= kLocalFlagRotated;
+    const size_t table_bytes = rotated ? static_cast<size_t>(rot->rot_dim) * sizeof(float) : 0;
+    const size_t ext = cast_end + (rotated ? sizeof(PackedLocalRotExt) + table_bytes : 0);
     std::vector<uint8_t> body(sizeof(h) + ext + n * 8 + blob_len);
     memcpy(body.data(), &h, sizeof(h));
     if (seg) {
@@ -195,6 +200,11 @@ std::vector<uint8_t> build_packed_local(PackedLocalHdr h, uint32_t n_segments,
     if (permuted) memcpy(body.data() + sizeof(h) + tset_end, perm, sizeof(*perm));
     if (transposed) memcpy(body.data() + sizeof(h) + perm_end, xpose, sizeof(*xpose));
     if (is_cast) memcpy(body.data() + sizeof(h) + xpose_end, cast, sizeof(*cast));
+    if (rotated) {
+        memcpy(body.data() + sizeof(h) + cast_end, rot, sizeof(*rot));
+        if (table_bytes)
+            memcpy(body.data() + sizeof(h) + cast_end + sizeof(*rot), rot_table, table_bytes);
+    }
     if (n) memcpy(body.data() + sizeof(h) + ext, offsets, n * 8);
     if (blob_len) memcpy(body.data() + sizeof(h) + ext + n * 8, keys_blob, blob_len);
     return body;
@@ -221,6 +231,12 @@ bool parse_packed_local(char op, const uint8_t* body, size_t body_len, PackedLoc
     const bool is_cast = (h.flags & kLocalFlagCast) != 0;
     if (is_cast && (h.flags & (kLocalFlagSliced | kLocalFlagTensorSet | kLocalFlagPermuted |
                                kLocalFlagTransposed)))
+        return false;
+    // A rotation is a read-side transform of whole, plainly laid out pages.
+    const bool rotated = (h.flags & kLocalFlagRotated) != 0;
+    if (rotated && (op != OP_R_FAST ||
+                    (h.flags & (kLocalFlagSliced | kLocalFlagTensorSet | kLocalFlagPermuted |
+                                kLocalFlagTransposed | kLocalFlagCast))))
         return false;
     if (h.flags & kLocalFlagSegmented) {
         if (body_len < pos + sizeof(PackedLocalSegExt)) return false;
@@ -313,6 +329,29 @@ bool parse_packed_local(char op, const uint8_t* body, size_t body_len, PackedLoc
                         PageSegments{out->n_segments, out->segment_stride}))
             return false;
         out->cast = e;
+    }
+    out->rot = PackedLocalRotExt{};
+    out->rot_table.clear();
+    if (rotated) {
+        if (body_len < pos + sizeof(PackedLocalRotExt)) return false;
+        PackedLocalRotExt e;
+        memcpy(&e, body + pos, sizeof(e));
+        pos += sizeof(e);
+        if (e.rsvd != 0) return false;
+        // Bounded before the table is sized; rotate_legal repeats it.
+        if (e.rot_dim > 2 * kMaxRotatePairs) return false;
+        const size_t table_bytes = static_cast<size_t>(e.rot_dim) * sizeof(float);
+        if (body_len - pos < table_bytes) return false;
+        out->rot_table.resize(e.rot_dim);
+        if (table_bytes) memcpy(out->rot_table.data(), body + pos, table_bytes);
+        pos += table_bytes;
+        // Plain rules, like the segments above; style == 0 fails rotate_legal,
+        // so a parsed request is rotated exactly when style != 0.
+        if (!rotate_legal(PageCodec::kNone, h.block_size,
+                          rotate_from_wire(e, out->rot_table.data()),
+                          PageSegments{out->n_segments, out->segment_stride}))
+            return false;
+        out->rot = e;
     }
     const size_t n = h.n_blocks;
     const size_t off_end = pos + n * 8;

@@ -59,7 +59,8 @@ constexpr char OP_STATS = 'Q';    // server stats JSON over the wire (extension)
 // [PackedLocalSliceExt when kLocalFlagSliced is set,] [PackedLocalTensorExt
 // when kLocalFlagTensorSet is set,] [PackedLocalPermExt when
 // kLocalFlagPermuted is set,] [PackedLocalXposeExt when kLocalFlagTransposed
-// is set,] [PackedLocalCastExt when kLocalFlagCast is set,] u64 offsets[n],
+// is set,] [PackedLocalCastExt when kLocalFlagCast is set,] [PackedLocalRotExt
+// and its rot_dim float32 table when kLocalFlagRotated is set,] u64 offsets[n],
 // NUL-separated key bytes (n keys).
 constexpr char OP_W_FAST = 'w';
 constexpr char OP_R_FAST = 'r';
@@ -178,6 +179,22 @@ struct PackedLocalCastExt {
 #pragma pack(pop)
 static_assert(sizeof(PackedLocalCastExt) == 16, "packed local cast extension size");
 
+// Follows PackedLocalHdr and every other extension when kLocalFlagRotated is
+// set, itself followed by rot_dim float32 values, (cos, sin) of pair 0, of
+// pair 1, ...: the rotation a READ applies to the K half of each page
+// (core/page_codec.h, PageRotate; docs/design.md, "rotated reads").
+#pragma pack(push, 1)
+struct PackedLocalRotExt {
+    uint32_t style;     // 1: NeoX halves, 2: GPT-J interleaved
+    uint32_t halves;    // 1 or 2; half 0 is rotated
+    uint32_t heads;
+    uint32_t head_dim;  // elements
+    uint32_t rot_dim;   // elements, <= head_dim
+    uint32_t rsvd;      // 0
+};
+#pragma pack(pop)
+static_assert(sizeof(PackedLocalRotExt) == 24, "packed local rotate extension size");
+
 // OP_TSET_REGISTER body: this header, then n_tensors records in set order.
 #pragma pack(push, 1)
 struct PackedTensorSetHdr {
@@ -240,6 +257,13 @@ constexpr uint32_t kLocalFlagTransposed = 128;
 // kLocalFlagSliced, kLocalFlagTensorSet, kLocalFlagPermuted or
 // kLocalFlagTransposed it is INVALID_REQ.
 constexpr uint32_t kLocalFlagCast = 256;
+// Rotate the K half of each page by the (cos, sin) table that follows the
+// PackedLocalRotExt after all other extensions (extension; OP_R_FAST only,
+// INVALID_REQ on OP_W_FAST). The pages are bf16 and block_size is the written
+// page. Together with kLocalFlagSliced, kLocalFlagTensorSet,
+// kLocalFlagPermuted, kLocalFlagTransposed or kLocalFlagCast it is
+// INVALID_REQ.
+constexpr uint32_t kLocalFlagRotated = 512;
 
 std::string op_name(char op);
 
@@ -319,7 +343,11 @@ std::vector<uint8_t> build_packed_local(PackedLocalHdr h, uint32_t n_segments,
                                         const PackedLocalTensorExt* tset = nullptr,
                                         const PackedLocalPermExt* perm = nullptr,
                                         const PackedLocalXposeExt* xpose = nullptr,
-                                        const PackedLocalCastExt* cast = nullptr);
+                                        const PackedLocalCastExt* cast = nullptr,
+                                        const PackedLocalRotExt* rot = nullptr,
+                                        const float* rot_table = nullptr);
+// (The rotate extension, the rot_dim floats at rot_table and kLocalFlagRotated
+// are written only for a `rot` with style != 0, its rsvd as given.)
 // (The cast extension and kLocalFlagCast are written only for a `cast` with
 // elem_type != 0.)
 // (The permute extension and kLocalFlagPermuted are written only for a `perm`
@@ -349,6 +377,8 @@ struct PackedLocalReq {
     PackedLocalPermExt perm{};  // rows == 0: not permuted
     PackedLocalXposeExt xpose{};  // tokens == 0: not transposed
     PackedLocalCastExt cast{};    // elem_type == 0: not cast
+    PackedLocalRotExt rot{};      // style == 0: not rotated
+    std::vector<float> rot_table;  // rot.rot_dim values when rotated
     std::vector<std::pair<std::string_view, uint64_t>> blocks;
 };
 // False (the server answers INVALID_REQ) for a truncated body or extension,
@@ -367,7 +397,10 @@ struct PackedLocalReq {
 // the geometry for block_size (same codec choice again). kLocalFlagCast is
 // refused next to any of those four flags, and when cast_legal refuses the
 // extension for block_size and the segments (same codec choice), which it
-// judges in place of segments_legal.
+// judges in place of segments_legal. kLocalFlagRotated is refused on
+// OP_W_FAST, next to any of those five flags, with a cut table, and when
+// rotate_legal refuses the geometry or the table for block_size and the
+// segments under plain rules.
 bool parse_packed_local(char op, const uint8_t* body, size_t body_len, PackedLocalReq* out);
 
 // Sentinel for duplicate-key allocations: the server returns rkey=0, addr=0

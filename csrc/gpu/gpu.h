@@ -293,6 +293,25 @@ bool launch_transform_blocks_cast(int dev, Stream s, PageCodec codec, PageDir di
 constexpr int kCastThreads = 256;
 constexpr int kCastFp8Threads = 512;
 
+// --- rotated reads (csrc/gpu/rotate.hip) ----------------------------------------
+// kLoad only: every stored block (plain bf16, fp8 or mxfp4, by `codec`) is
+// decoded to the bf16 page [halves, T, heads, head_dim] and handed to the
+// client with the rotary pairs of half 0 turned by rot.table (core/page_codec.h,
+// PageRotate; docs/design.md, "rotated reads"), in seg.n segments when
+// seg.n > 1. fp8 reads block i's scale from dev_scales[i]; the other codecs
+// ignore dev_scales. rot.table is host memory and is copied into the kernel
+// arguments before the call returns. There is no byte fallback: false before
+// any launch, with last_error() set, for a geometry or a table rotate_legal
+// refuses, unless aligned16 holds (every descriptor pointer is a multiple of
+// 16; the CALLER checks), or for a page or a grid that does not fit 31 bits of
+// lane units or workgroups.
+bool launch_load_rotated(int dev, Stream s, PageCodec codec, const uint64_t* dev_src,
+                         const uint64_t* dev_dst, const float* dev_scales, int n_blocks,
+                         size_t elems_per_block, bool aligned16, PageSegments seg,
+                         const PageRotate& rot);
+// Workgroup size of the rotate kernels, a (block, segment, chunk) each.
+constexpr int kRotateThreads = 256;
+
 // --- block fingerprint ------------------------------------------------------
 // 64-bit position-salted fingerprint per block -> out_hashes[i] (device mem).
 bool launch_hash_blocks(int dev, Stream s, const uint64_t* dev_ptrs, int n_blocks,

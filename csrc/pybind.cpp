@@ -23,6 +23,7 @@
 #include "core/mempool.h"
 #include "gpu/fp8_codec.h"
 #include "gpu/mxfp4_codec.h"
+#include "gpu/rotate_math.h"
 #include "gpu/gpu.h"
 #include "server/completed_prefix.h"
 #include "server/server.h"
@@ -713,6 +714,71 @@ std::pair<bool, std::vector<float>> transform_blocks_cast_py(
     return {ok, scales};
 }
 
+// ---- rotated reads (docs/design.md, "rotated reads") ---------------------------
+// A rotation from Python: None, or (style, halves, heads, head_dim, rot_dim,
+// table), the table a float32 buffer of rot_dim values, (cos, sin) per pair.
+// The PageRotate points into the holder's own copy of the table.
+struct RotatePy {
+    PageRotate r;
+    std::vector<float> table;
+};
+
+void rotate_from_py(const char* what, const py::object& o, RotatePy* out, size_t extra = 0) {
+    out->r = PageRotate{};
+    out->table.clear();
+    if (o.is_none()) return;
+    py::tuple t = o.cast<py::tuple>();
+    if (t.size() != 6 && t.size() != 6 + extra)
+        throw std::invalid_argument(
+            std::string(what) +
+            ": a rotation is (style, halves, heads, head_dim, rot_dim, float32 table)");
+    out->r.style = t[0].cast<uint32_t>();
+    out->r.halves = t[1].cast<uint32_t>();
+    out->r.heads = t[2].cast<uint32_t>();
+    out->r.head_dim = t[3].cast<uint32_t>();
+    out->r.rot_dim = t[4].cast<uint32_t>();
+    py::buffer_info b = t[5].cast<py::buffer>().request();
+    if (b.itemsize != 4 || b.format != py::format_descriptor<float>::format() ||
+        static_cast<uint64_t>(b.size) != out->r.rot_dim)
+        throw std::invalid_argument(std::string(what) +
+                                    ": the table is rot_dim contiguous float32 values");
+    out->table.assign(static_cast<const float*>(b.ptr),
+                      static_cast<const float*>(b.ptr) + b.size);
+    out->r.table = out->table.data();
+}
+
+// The rotate launcher, called directly: one stored block and one client page
+// pointer per block, scales for fp8 (one per block). Returns what the
+// launcher returns.
+bool load_rotated_py(int codec_id, const std::vector<uint64_t>& stored,
+                     const std::vector<uint64_t>& client, const std::vector<float>& scales,
+                     size_t elems_per_block, const py::object& rotate, uint32_t n_segments,
+                     uint64_t segment_stride, int device) {
+    const char* what = "_dbg_load_rotated";
+    const PageCodec codec = codec_from_id(what, codec_id);
+    RotatePy rp;
+    rotate_from_py(what, rotate, &rp);
+    require_gpu_and_pairs(what, stored, client);
+    size_t n = stored.size();
+    if (page_codec_info(codec).page_scale && scales.size() != n)
+        throw std::invalid_argument(std::string(what) + ": one scale per block");
+    py::gil_scoped_release rel;
+    Pinned<uint64_t> h_stored(n ? n : 1), h_client(n ? n : 1);
+    Pinned<float> h_scale(n ? n : 1);
+    memcpy(h_stored.p, stored.data(), n * 8);
+    memcpy(h_client.p, client.data(), n * 8);
+    memcpy(h_scale.p, scales.data(), std::min(scales.size(), n) * sizeof(float));
+    ScopedStream st(device);
+    bool ok = gpu::launch_load_rotated(device, st.s, codec, h_stored.p, h_client.p, h_scale.p,
+                                       static_cast<int>(n), elems_per_block,
+                                       all_aligned16(stored, client),
+                                       PageSegments{n_segments, segment_stride}, rp.r);
+    // Always drain the stream before the pinned descriptors go away.
+    if (!gpu::stream_sync(st.s))
+        throw std::runtime_error(std::string(what) + " failed: " + gpu::last_error());
+    return ok;
+}
+
 // (codec id, stored bytes) of a request with these flags and this logical
 // page size, by the codec table alone (host-only).
 std::pair<int, size_t> page_codec_py(uint32_t flags, size_t page_bytes) {
@@ -1080,7 +1146,11 @@ PYBIND11_MODULE(_native, m) {
                bool sync_response, uint32_t extra_flags, uint32_t n_segments,
                uint64_t segment_stride, const py::object& page_slice,
                const py::object& page_permute, const py::object& page_transpose,
-               const py::object& page_cast) {
+               const py::object& page_cast, const py::object& page_rotate) {
+                // page_rotate: None or rotate_from_py's tuple of 6; reads only
+                RotatePy rp;
+                rotate_from_py("rw_local", page_rotate, &rp);
+                const PackedLocalRotExt re = rotate_to_wire(rp.r);
                 // page_cast: None or cast_from_py's tuple of 4; block_size is
                 // then the logical bf16 size and element_size the client's 1
                 const PackedLocalCastExt ce = cast_to_wire(cast_from_py("rw_local", page_cast));
@@ -1118,14 +1188,15 @@ PYBIND11_MODULE(_native, m) {
                                          byte_offs.data(), n, block_size, ptr, device,
                                          sync_response, nullptr, extra_flags, n_segments,
                                          segment_stride * element_size, &sl, nullptr, &pe, &xe,
-                                         &ce);
+                                         &ce, &re, rp.table.data());
             },
             py::arg("op"), py::arg("keys"), py::arg("offsets"), py::arg("element_size"),
             py::arg("block_size"), py::arg("ptr"), py::arg("device"),
             py::arg("sync_response") = false, py::arg("extra_flags") = 0,
             py::arg("n_segments") = 1, py::arg("segment_stride") = 0,
             py::arg("page_slice") = py::none(), py::arg("page_permute") = py::none(),
-            py::arg("page_transpose") = py::none(), py::arg("page_cast") = py::none())
+            py::arg("page_transpose") = py::none(), py::arg("page_cast") = py::none(),
+            py::arg("page_rotate") = py::none())
         .def(
             "rw_local_blob",
             [](ClientConn& c, const std::string& op, py::buffer blob, py::buffer offsets,
@@ -1133,7 +1204,11 @@ PYBIND11_MODULE(_native, m) {
                bool sync_response, uint32_t extra_flags, uint32_t n_segments,
                uint64_t segment_stride, const py::object& page_slice,
                const py::object& page_permute, const py::object& page_transpose,
-               const py::object& page_cast) {
+               const py::object& page_cast, const py::object& page_rotate) {
+                // page_rotate: None or rotate_from_py's tuple of 6; reads only
+                RotatePy rp;
+                rotate_from_py("rw_local", page_rotate, &rp);
+                const PackedLocalRotExt re = rotate_to_wire(rp.r);
                 // page_cast: None or cast_from_py's tuple of 4; block_size is
                 // then the logical bf16 size and element_size the client's 1
                 const PackedLocalCastExt ce = cast_to_wire(cast_from_py("rw_local", page_cast));
@@ -1164,21 +1239,25 @@ PYBIND11_MODULE(_native, m) {
                                          n, block_size, ptr, device, sync_response, nullptr,
                                          extra_flags, n_segments,
                                          segment_stride * element_size, &sl, nullptr, &pe, &xe,
-                                         &ce);
+                                         &ce, &re, rp.table.data());
             },
             py::arg("op"), py::arg("blob"), py::arg("offsets"), py::arg("element_size"),
             py::arg("block_size"), py::arg("ptr"), py::arg("device"),
             py::arg("sync_response") = false, py::arg("extra_flags") = 0,
             py::arg("n_segments") = 1, py::arg("segment_stride") = 0,
             py::arg("page_slice") = py::none(), py::arg("page_permute") = py::none(),
-            py::arg("page_transpose") = py::none(), py::arg("page_cast") = py::none())
+            py::arg("page_transpose") = py::none(), py::arg("page_cast") = py::none(),
+            py::arg("page_rotate") = py::none())
         .def(
             "rw_local_blob_async",
             [](ClientConn& c, const std::string& op, py::buffer blob, py::buffer offsets,
                uint64_t element_size, int block_size, uintptr_t ptr, int device,
                uint32_t n_segments, uint64_t segment_stride, const py::object& page_slice,
                const py::object& page_permute, const py::object& page_transpose,
-               const py::object& page_cast) {
+               const py::object& page_cast, const py::object& page_rotate) {
+                RotatePy rp;
+                rotate_from_py("rw_local", page_rotate, &rp);
+                const PackedLocalRotExt re = rotate_to_wire(rp.r);
                 const PackedLocalCastExt ce = cast_to_wire(cast_from_py("rw_local", page_cast));
                 const PackedLocalXposeExt xe =
                     transpose_to_wire(xpose_from_py("rw_local", page_transpose));
@@ -1207,7 +1286,7 @@ PYBIND11_MODULE(_native, m) {
                                             byte_offs.data(), n, block_size, ptr, device,
                                             /*sync_response=*/true, &ticket, 0, n_segments,
                                             segment_stride * element_size, &sl, nullptr,
-                                            &pe, &xe, &ce);
+                                            &pe, &xe, &ce, &re, rp.table.data());
                 }
                 return py::make_tuple(ret, ticket);
             },
@@ -1215,7 +1294,8 @@ PYBIND11_MODULE(_native, m) {
             py::arg("block_size"), py::arg("ptr"), py::arg("device"),
             py::arg("n_segments") = 1, py::arg("segment_stride") = 0,
             py::arg("page_slice") = py::none(), py::arg("page_permute") = py::none(),
-            py::arg("page_transpose") = py::none(), py::arg("page_cast") = py::none())
+            py::arg("page_transpose") = py::none(), py::arg("page_cast") = py::none(),
+            py::arg("page_rotate") = py::none())
         .def(
             "rw_tset_blob",
             [](ClientConn& c, const std::string& op, py::buffer blob, py::buffer offsets,
@@ -1659,6 +1739,41 @@ PYBIND11_MODULE(_native, m) {
           py::arg("device"), py::arg("n_streams"), py::arg("slots_per_stream"),
           py::arg("max_descs_per_slot"), py::arg("copy_jobs"), py::arg("casts"),
           py::arg("n_threads"), py::arg("timeout_s"));
+    // The rotation predicate; the rotation is rotate_from_py's tuple of 6, the
+    // client segments as above.
+    m.def("_dbg_rotate_legal",
+          [](int codec, size_t page_bytes, const py::object& rotate, uint32_t n_segments,
+             uint64_t stride_bytes) {
+              if (rotate.is_none())
+                  throw std::invalid_argument("_dbg_rotate_legal: a rotation is a tuple of 6");
+              RotatePy rp;
+              rotate_from_py("_dbg_rotate_legal", rotate, &rp);
+              return rotate_legal(codec_from_id("_dbg_rotate_legal", codec), page_bytes, rp.r,
+                                  PageSegments{n_segments, stride_bytes});
+          },
+          py::arg("codec"), py::arg("page_bytes"), py::arg("rotate"), py::arg("n_segments") = 1,
+          py::arg("stride_bytes") = 0);
+    m.attr("_ROTATE_THREADS") = gpu::kRotateThreads;
+    m.attr("_MAX_ROTATE_PAIRS") = kMaxRotatePairs;
+    // The rotate launcher (gpu.h), called directly. Returns False for what the
+    // launcher refuses.
+    m.def("_dbg_load_rotated", &load_rotated_py, py::arg("codec"), py::arg("stored_ptrs"),
+          py::arg("client_ptrs"), py::arg("scales"), py::arg("elems_per_block"),
+          py::arg("rotate"), py::arg("n_segments") = 1, py::arg("segment_stride") = 0,
+          py::arg("device") = 0);
+    // The scalar rule of a rotary pair on the host (csrc/gpu/rotate_math.h):
+    // bf16 bits a[i], b[i] under (cos, sin) -> the bits of (out_a, out_b).
+    m.def("_dbg_rotate_pairs", [](py::buffer a_bits, py::buffer b_bits, float c, float s) {
+        py::buffer_info a = a_bits.request(), b = b_bits.request();
+        if (a.itemsize != 2 || b.itemsize != 2 || a.size != b.size)
+            throw std::invalid_argument("_dbg_rotate_pairs takes two equal uint16 buffers");
+        std::vector<uint16_t> oa(static_cast<size_t>(a.size)), ob(oa.size());
+        for (size_t i = 0; i < oa.size(); i++)
+            rotate::pair_bf16(static_cast<const uint16_t*>(a.ptr)[i],
+                              static_cast<const uint16_t*>(b.ptr)[i], c, s, &oa[i], &ob[i]);
+        return py::make_tuple(py::bytes(reinterpret_cast<const char*>(oa.data()), oa.size() * 2),
+                              py::bytes(reinterpret_cast<const char*>(ob.data()), ob.size() * 2));
+    });
     // The scalar rules of a cast page on the host (csrc/gpu/fp8_codec.h): codes
     // -> bf16 bits under a scale, and bf16 bits -> codes under inv = 1 / scale.
     m.def("_dbg_cast_store", [](py::buffer codes, float scale) {
@@ -1702,7 +1817,14 @@ PYBIND11_MODULE(_native, m) {
              const std::vector<uint64_t>& offsets, const std::vector<std::string>& keys,
              uint32_t n_segments, uint64_t segment_stride, const py::object& slice,
              const py::object& tensor_set, const py::object& permute,
-             const py::object& transpose, const py::object& cast) {
+             const py::object& transpose, const py::object& cast, const py::object& rotate) {
+              // None, or rotate_from_py's tuple of 6, optionally with rsvd as
+              // a seventh value, written as given
+              RotatePy rp;
+              rotate_from_py("_dbg_build_packed_local", rotate, &rp, 1);
+              PackedLocalRotExt re = rotate_to_wire(rp.r);
+              if (!rotate.is_none() && py::len(rotate) == 7)
+                  re.rsvd = rotate.cast<py::tuple>()[6].cast<uint32_t>();
               // None, or cast_from_py's tuple of 4, written as given
               const PackedLocalCastExt ce =
                   cast_to_wire(cast_from_py("_dbg_build_packed_local", cast));
@@ -1766,7 +1888,7 @@ PYBIND11_MODULE(_native, m) {
               auto v = build_packed_local(h, n_segments, segment_stride, offsets.data(),
                                           blob.data(), blob.size(), &sl,
                                           tensor_set.is_none() ? nullptr : &ts, &pe, &xe,
-                                          &ce);
+                                          &ce, &re, rp.table.data());
               return py::bytes(reinterpret_cast<const char*>(v.data()), v.size());
           },
           py::arg("device"), py::arg("pid"), py::arg("base_ptr"), py::arg("base_offset"),
@@ -1774,7 +1896,8 @@ PYBIND11_MODULE(_native, m) {
           py::arg("offsets"), py::arg("keys"), py::arg("n_segments") = 1,
           py::arg("segment_stride") = 0, py::arg("slice") = py::none(),
           py::arg("tensor_set") = py::none(), py::arg("permute") = py::none(),
-          py::arg("transpose") = py::none(), py::arg("cast") = py::none());
+          py::arg("transpose") = py::none(), py::arg("cast") = py::none(),
+          py::arg("rotate") = py::none());
     m.def("_dbg_parse_packed_local", [](const std::string& op, py::bytes data) {
         std::string s = data;
         PackedLocalReq r;
@@ -1822,6 +1945,14 @@ PYBIND11_MODULE(_native, m) {
                                        r.cast.scale[1]);
         else
             d["cast"] = py::none();
+        // None, or (style, halves, heads, head_dim, rot_dim, table bytes)
+        if (r.rot.style)
+            d["rotate"] = py::make_tuple(
+                r.rot.style, r.rot.halves, r.rot.heads, r.rot.head_dim, r.rot.rot_dim,
+                py::bytes(reinterpret_cast<const char*>(r.rot_table.data()),
+                          r.rot_table.size() * sizeof(float)));
+        else
+            d["rotate"] = py::none();
         py::list offs, keys;
         for (auto& [key, off] : r.blocks) {
             offs.append(off);

@@ -547,6 +547,8 @@ bool parse_packed_local(char op, const uint8_t* body, size_t body_len, Server::L
     v->perm = permute_from_wire(req.perm);
     v->xpose = transpose_from_wire(req.xpose);
     v->cast = cast_from_wire(req.cast);
+    v->rot = rotate_from_wire(req.rot, nullptr);
+    v->rot_table = std::move(req.rot_table);
     v->ipc = body + offsetof(PackedLocalHdr, ipc);
     v->ipc_len = 64;
     v->blocks = std::move(req.blocks);
@@ -1110,6 +1112,15 @@ void Server::op_local_read(Conn* c, const LocalView& msg, const ReqCtx& ctx) {
                        !transpose_legal(PageCodec::kNone, page, msg.xpose, client_seg) ||
                        (msg.n_segments != 1 && msg.segment_stride % 16 != 0)))
         return reply_local(c, ctx, INVALID_REQ);
+    // Rotated read: plain rules here, every entry against its own codec in
+    // the sweep; nothing else next to it. rotate_legal covers the stride.
+    PageRotate rot = msg.rot;
+    rot.table = msg.rot_table.data();
+    const bool rotated = rotate_is_set(rot);
+    if (rotated && (sliced || tset || permuted || transposed || is_cast ||
+                    msg.rot_table.size() != rot.rot_dim ||
+                    !rotate_legal(PageCodec::kNone, page, rot, client_seg)))
+        return reply_local(c, ctx, INVALID_REQ);
 
     auto tr0 = Clock::now();
     // Group blocks by the shard whose GPU EXECUTES the copy. For same-GPU
@@ -1201,6 +1212,18 @@ void Server::op_local_read(Conn* c, const LocalView& msg, const ReqCtx& ctx) {
                     err = INVALID_REQ;
                     return false;
                 }
+            } else if (rotated) {
+                // As for a slice: the page is the written size for every
+                // codec (T is implied by it, and a shorter page would cut the
+                // halves elsewhere), the rotation legal for the entry's codec,
+                // and a 16-byte-aligned client address, because the rotate
+                // kernels have no byte path.
+                if (!stored_matches(e->codec, e->size, page) ||
+                    !rotate_legal(e->codec, page, rot, client_seg) ||
+                    (client_addr + b.second) % 16 != 0) {
+                    err = INVALID_REQ;
+                    return false;
+                }
             } else if (tset) {
                 // The whole request against the entry's codec (geometry,
                 // aligned bases and offsets), once per codec; the page must
@@ -1243,6 +1266,10 @@ void Server::op_local_read(Conn* c, const LocalView& msg, const ReqCtx& ctx) {
                     it->second.perm = msg.perm;
                     it->second.xpose = msg.xpose;
                     it->second.cast = msg.cast;
+                    if (rotated) {
+                        it->second.rot = msg.rot;
+                        it->second.rot_table = msg.rot_table;
+                    }
                     if (tset) {
                         it->second.tensor_bases = tset->bases;
                         it->second.segs_per_tensor =

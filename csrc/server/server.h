@@ -168,6 +168,13 @@ class Server {
         // the logical bf16 size and the segments speak of client bytes. Never
         // together with a slice, a tensor set, a permutation or a transpose.
         PageCast cast;
+        // Rotated reads (OP_R_FAST only): rot.style != 0 says that the K half
+        // of every page is turned by rot_table, rot.rot_dim (cos, sin) floats,
+        // while it loads. rot.table is not set here: the read path points it
+        // at rot_table. Never together with a slice, a tensor set, a
+        // permutation, a transpose or a cast.
+        PageRotate rot;
+        std::vector<float> rot_table;
         const uint8_t* ipc = nullptr;
         size_t ipc_len = 0;
         std::vector<std::pair<std::string_view, uint64_t>> blocks;

@@ -243,6 +243,16 @@ bool Shard::submit_copy(CopyJob&& job) {
     // So is a cast: next to none of the four.
     const bool is_cast = cast_is_set(job.cast);
     if (is_cast && (sliced || tset || permuted || transposed)) return false;
+    // A rotation is a read-side transform of whole pages: next to none of the
+    // five, with the table the job owns.
+    const bool rotated = rotate_is_set(job.rot);
+    if (rotated) {
+        if (job.rot_table.size() != job.rot.rot_dim) return false;
+        job.rot.table = job.rot_table.data();
+        if (job.dir != PageDir::kLoad || sliced || tset || permuted || transposed || is_cast ||
+            !rotate_legal(job.codec, job.bytes_per_block, job.rot, seg))
+            return false;
+    }
     // A codec with a per-page scale needs one scale slot per block.
     const bool page_scale = page_codec_info(job.codec).page_scale;
     if (page_scale && (!job.scales || job.scales->size() < job.scales_off + n)) return false;
@@ -270,6 +280,8 @@ bool Shard::submit_copy(CopyJob&& job) {
             sub.perm = job.perm;
             sub.xpose = job.xpose;
             sub.cast = job.cast;
+            sub.rot = job.rot;
+            sub.rot_table = job.rot_table;
             sub.scales = job.scales;
             sub.scales_off = job.scales_off + off;
             sub.src.assign(job.src.begin() + static_cast<long>(off),
@@ -289,7 +301,7 @@ bool Shard::submit_copy(CopyJob&& job) {
     }
 
     if (!on_gpu()) {
-        if (transforms) return false;  // GPU-only
+        if (transforms || rotated) return false;  // GPU-only
         // CPU shard: copies run inline on the caller (loop) thread.
         // A segmented page: the client side steps by the stride, the pool
         // side by the segment.
@@ -436,6 +448,8 @@ bool Shard::submit_copy(CopyJob&& job) {
     if (!aligned && transposed) return false;
     // Nor the cast kernels; cast_legal has judged their segments and stride.
     if (!aligned && is_cast) return false;
+    // Nor the rotate kernels, for any codec.
+    if (!aligned && rotated) return false;
 
     // HIP stream enqueues are thread-safe; each job's ops precede its event
     // in stream order regardless of interleaving with other submitters, so
@@ -472,7 +486,7 @@ bool Shard::submit_copy(CopyJob&& job) {
     // (Segmented, sliced and tensor-set jobs always use the pinned-descriptor
     // kernels.)
     if (aligned && n <= 16 && !transforms && !segmented && !sliced && !tset && !permuted &&
-        !transposed && !is_cast) {
+        !transposed && !is_cast && !rotated) {
         Slot* slot = acquire_slot(sc);
         if (!slot) return false;
         bool ok = gpu::set_device(opt_.device) &&
@@ -581,6 +595,16 @@ bool Shard::submit_copy(CopyJob&& job) {
                                slot->h_scale, static_cast<int>(take),
                                job.bytes_per_block / kPageElemBytes, aligned, seg, job.cast);
             }
+        } else if (rotated) {
+            // One launcher for every codec; fp8's scales ride in h_scale, and
+            // the table goes into each launch's kernel arguments.
+            if (page_scale)
+                memcpy(slot->h_scale, job.scales->data() + job.scales_off + off,
+                       take * sizeof(float));
+            ok = ok && gpu::launch_load_rotated(opt_.device, sc.stream, job.codec, dsrc, ddst,
+                                                slot->h_scale, static_cast<int>(take),
+                                                job.bytes_per_block / kPageElemBytes, aligned,
+                                                seg, job.rot);
         } else if (!transforms) {
             ok = ok && gpu::launch_copy_blocks(opt_.device, sc.stream, dsrc, ddst,
                                                static_cast<int>(take), job.bytes_per_block,

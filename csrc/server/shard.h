@@ -94,6 +94,16 @@ class Shard {
         // permutation or transpose; on the GPU it needs 16-byte-aligned
         // pointers for every codec.
         PageCast cast;
+        // Rotated reads (core/page_codec.h, rotate_legal): with rot.style != 0
+        // a kLoad job turns the rotary pairs of every page's K half while it
+        // loads, for every codec. The job OWNS the table: rot_table holds
+        // rot.rot_dim floats and submit_copy points rot.table at it, so the
+        // caller's table may go away once the job has been built. Such a job
+        // never takes the inline-argument path and carries no slice, tensor
+        // set, permutation, transpose or cast; on the GPU it needs
+        // 16-byte-aligned pointers and stride for every codec.
+        PageRotate rot;
+        std::vector<float> rot_table;
         // Codecs with a per-page scale: block i's scale is
         // (*scales)[scales_off + i], written before done() by kStore and
         // read at submit by kLoad. Fan-out sub-jobs share the vector.

@@ -11,6 +11,7 @@ from .lib import (
     PagePermute,
     PageTranspose,
     PageCast,
+    PageRotate,
     TensorSet,
     DisableTorchCaching,
     ClientConfig,
@@ -41,6 +42,7 @@ __all__ = [
     "PagePermute",
     "PageTranspose",
     "PageCast",
+    "PageRotate",
     "TensorSet",
     "DisableTorchCaching",
     "register_server",

@@ -29,6 +29,7 @@ SOURCES = [
     CSRC / "gpu" / "quant_error.hip",
     CSRC / "gpu" / "transpose.hip",
     CSRC / "gpu" / "cast.hip",
+    CSRC / "gpu" / "rotate.hip",
     CSRC / "fabric" / "verbs_fabric.cpp",
     CSRC / "server" / "shard.cpp",
     CSRC / "server" / "kv_index.cpp",
@@ -46,6 +47,7 @@ HIP_EXTRA_FLAGS = {
     "quant_error.hip": _NO_PACKED_FP32,
     "transpose.hip": _NO_PACKED_FP32,
     "cast.hip": _NO_PACKED_FP32,
+    "rotate.hip": _NO_PACKED_FP32,
 }
 
 HEADERS = sorted((CSRC).rglob("*.h")) + [Path(__file__)]

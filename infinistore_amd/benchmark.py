@@ -102,6 +102,14 @@ def parse_args():
                    help="with --fp8-cache: what an fp8 engine does without cast pages, "
                         "whole bf16 pages through a staging tensor plus a torch "
                         "scale-and-cast (inside the timed windows), both ways")
+    p.add_argument("--rotate", type=float, default=None, metavar="DELTA",
+                   help="rotated reads (local-GPU path): the buffers are bf16 pages "
+                        "[2, T, 8, 128] and every read shifts the RoPE position of the K "
+                        "half by DELTA (NeoX pairs, theta 10000), for every --quant")
+    p.add_argument("--rotate-baseline", action="store_true",
+                   help="with --rotate: what a reader does without rotated reads, a whole "
+                        "read, then a torch pass over the K half of each buffer (inside "
+                        "the timed read)")
     p.add_argument("--verify", action="store_true")
     p.add_argument("--json", action="store_true", help="print a JSON summary")
     p.add_argument("--spawn-server", action="store_true",
@@ -155,6 +163,24 @@ def bf16_to_codes(pages, out):
     out.view(torch.float8_e4m3fn).view(pages.shape).copy_(y.to(torch.float8_e4m3fn))
 
 
+# --rotate: heads and head_dim of the pages, [2, T, ROT_HEADS, ROT_HEAD_DIM] bf16.
+ROT_HEADS, ROT_HEAD_DIM = 8, 128
+
+
+def rotate_k(buf, page_elems, rot, out=None):
+    """The torch pass a reader needs after a whole read: the formula of the
+    rotate kernels over the K half of every page of `buf`, into `out` (in
+    place by default)."""
+    out = buf if out is None else out
+    k, o = (t.view(-1, 2, page_elems // 2)[:, 0].unflatten(-1, (-1, rot.head_dim))
+            for t in (buf, out))
+    P = rot.rot_dim // 2
+    cs = torch.from_numpy(rot.cos_sin).to(buf.device)
+    a, b = k[..., :P].float(), k[..., P:2 * P].float()
+    o[..., :P] = (a * cs[:, 0] - b * cs[:, 1]).to(buf.dtype)
+    o[..., P:2 * P] = (b * cs[:, 0] + a * cs[:, 1]).to(buf.dtype)
+
+
 def slice_geometry(args):
     """(h0, h1, H, rows, head_elems) of --slice, or None. The page is viewed as
     [rows, H, head_elems]."""
@@ -199,8 +225,9 @@ def make_buffers(args, conn, local, device):
     total_bytes = args.size << 20
     n_blocks = total_bytes // block_bytes
     per_step = max(1, n_blocks // args.steps)
-    dt = torch.bfloat16 if args.quant else torch.float32
-    es = 2 if args.quant or args.fp8_cache else 4
+    bf16 = args.quant or args.rotate is not None
+    dt = torch.bfloat16 if bf16 else torch.float32
+    es = 2 if bf16 or args.fp8_cache else 4
 
     cap = (1 << 30) + (1 << 28)  # 1.25 GiB
     n_sub = max(1, -(-total_bytes // cap))
@@ -316,7 +343,7 @@ def run_once(args, conn, local, device, bufs=None):
     block_bytes = args.block_size << 10
     total_bytes = args.size << 20
     n_blocks = total_bytes // block_bytes
-    es = 2 if args.quant or args.fp8_cache else 4
+    es = 2 if args.quant or args.fp8_cache or args.rotate is not None else 4
     page_elems = block_bytes // es
 
     srcs, dsts, blocks_per_sub = (bufs if bufs is not None
@@ -368,6 +395,11 @@ def run_once(args, conn, local, device, bufs=None):
         stages = [torch.zeros(d.numel() // page_elems, 2, page_elems // 2, dtype=torch.bfloat16,
                               device=d.device) for d in dsts]
         torch.cuda.synchronize()
+
+    # --rotate: one table for the run; the baseline reads whole pages.
+    rot = (lib.PageRotate.from_delta(args.rotate, ROT_HEADS, ROT_HEAD_DIM)
+           if local and args.rotate is not None else None)
+    rot_kw = {"page_rotate": rot} if rot and not args.rotate_baseline else {}
 
     def geom(t, permuted=True):  # geometry arguments for sub-tensor t
         g = {}
@@ -438,9 +470,15 @@ def run_once(args, conn, local, device, bufs=None):
                 tickets.append(conn.read_pages_async(
                     stages[t_idx].view(-1) if stages else dsts[t_idx], ks, offs, page_elems,
                     **geom(dsts[t_idx],
-                           permuted=not (args.hnd_baseline or args.pa_baseline))))
+                           permuted=not (args.hnd_baseline or args.pa_baseline)), **rot_kw))
         for tk in tickets:
             conn.wait_read(tk)
+        if rot and args.rotate_baseline:
+            # the second pass a reader needs today: the whole pages landed,
+            # their keys still carry the position they were written at
+            for d in dsts:
+                rotate_k(d, page_elems, rot)
+            torch.cuda.synchronize()
         if stages:
             # the second pass an fp8 engine needs today: bf16 pages landed in
             # the staging tensors, its cache wants codes
@@ -505,6 +543,17 @@ def run_once(args, conn, local, device, bufs=None):
             codes_to_bf16(b, vb)
             assert _close(va.cpu(), vb.cpu(), args.quant, extra=2.0 ** -4), \
                 "verification failed (fp8 cache)"
+    elif args.verify and rot:
+        # the torch formula over the written pages; an input error of the
+        # codec's bound grows by |cos| + |sin| <= sqrt(2), and both sides round
+        # a result below 2 to bf16, half an ulp of 2^-7 each
+        tol = 1.4143 * _QUANT_TOL.get(args.quant, 0.0) + 2.0 ** -7
+        for a, b in zip(srcs, dsts):
+            want = torch.empty_like(a)
+            want.copy_(a)
+            rotate_k(a, page_elems, rot, out=want)
+            err = float((want.float() - b.to(want.device).float()).abs().max())
+            assert err <= tol, f"verification failed (rotate): {err} > {tol}"
     elif args.verify:
         for a, b in zip(srcs, hnd_outs or pa_outs or dsts):
             assert _close(a.cpu(), b.cpu(), args.quant), "verification failed"
@@ -701,6 +750,15 @@ def main():
         raise SystemExit("--fp8-cache needs --local-gpu, one client, a page of whole "
                          "64-element halves and no --segments, --slice, --fused-layers, "
                          "--hnd or --pa")
+    if args.rotate_baseline and args.rotate is None:
+        raise SystemExit("--rotate-baseline needs --rotate")
+    if args.rotate is not None and (
+            not args.local_gpu or args.segments != 1 or args.slice or args.fused_layers
+            or args.hnd or args.pa or args.fp8_cache or args.clients > 1
+            or (args.block_size << 10) % (2 * ROT_HEADS * ROT_HEAD_DIM * 2)):
+        raise SystemExit("--rotate needs --local-gpu, one client, a page of whole "
+                         f"[2, {ROT_HEADS}, {ROT_HEAD_DIM}] bf16 tokens and no --segments, "
+                         "--slice, --fused-layers, --hnd, --pa or --fp8-cache")
     if args.slice:
         if not args.local_gpu or args.segments != 1:
             raise SystemExit("--slice needs --local-gpu and --segments 1")

@@ -129,11 +129,11 @@ class PagedKVConnector:
     def load_layer(self, layer: int, kv_out: torch.Tensor, page_keys: List[str],
                    page_offsets, page_elems: int, segments: int = 1,
                    segment_stride: int = 0, page_slice=None, page_permute=None,
-                   page_transpose=None, page_cast=None) -> bool:
+                   page_transpose=None, page_cast=None, page_rotate=None) -> bool:
         """Gather this layer's cached pages into the engine's KV tensor.
         Returns False if any page is missing (caller falls back to compute).
         segments / segment_stride / page_slice / page_permute / page_transpose /
-        page_cast: as in
+        page_cast / page_rotate: as in
         InfinityConnection.read_pages (page_elems is then the sliced page); a
         refused geometry raises ValueError."""
         keys = [self._key(layer, k) for k in page_keys]
@@ -143,6 +143,8 @@ class PagedKVConnector:
             raise ValueError("transposed pages use the local GPU path")
         if page_cast is not None and not self.local:
             raise ValueError("cast pages use the local GPU path")
+        if page_rotate is not None and not self.local:
+            raise ValueError("rotated reads use the local GPU path")
         if segments != 1 and not self.local:
             raise ValueError("segmented pages use the local GPU path")
         if page_slice is not None and not self.local:
@@ -156,7 +158,8 @@ class PagedKVConnector:
                                      segment_stride=segment_stride,
                                      page_slice=page_slice,
                                      page_permute=page_permute,
-                                     page_transpose=page_transpose, page_cast=page_cast)
+                                     page_transpose=page_transpose, page_cast=page_cast,
+                                     page_rotate=page_rotate)
             else:
                 self._ensure_mr(kv_out)
                 blocks = [(k, int(o)) for k, o in zip(keys, page_offsets)]
@@ -164,9 +167,9 @@ class PagedKVConnector:
             self.conn.sync()
             return True
         except ValueError:
-            if page_transpose is None and page_cast is None:
+            if page_transpose is None and page_cast is None and page_rotate is None:
                 return False
-            raise  # a transposed or cast read's arguments are checked by read_pages alone
+            raise  # a transposed, cast or rotated read's arguments are checked by read_pages alone
         except Exception:
             return False
 
@@ -174,18 +177,20 @@ class PagedKVConnector:
                          page_keys: List[str], page_offsets, page_elems: int,
                          segments: int = 1, segment_stride: int = 0,
                          page_slice=None, page_permute=None, page_transpose=None,
-                         page_cast=None):
+                         page_cast=None, page_rotate=None):
         """Ticketed prefetch (local path): push the gather and return a
         ticket; call wait_load(ticket) before touching kv_out. Lets decode
         overlap the next request's KV fetch with current compute. Returns
         None if any page was missing or the path is unavailable (caller
         falls back to load_layer / recompute). page_slice, page_permute,
-        page_transpose and page_cast as in load_layer."""
+        page_transpose, page_cast and page_rotate as in load_layer."""
         self.conn._permute_arg(page_permute, page_elems, segments, None, page_slice)
         if page_transpose is not None and not self.local:
             raise ValueError("transposed pages use the local GPU path")
         if page_cast is not None and not self.local:
             raise ValueError("cast pages use the local GPU path")
+        if page_rotate is not None and not self.local:
+            raise ValueError("rotated reads use the local GPU path")
         if not self.local:
             if segments != 1:
                 raise ValueError("segmented pages use the local GPU path")
@@ -202,9 +207,10 @@ class PagedKVConnector:
                                               page_slice=page_slice,
                                               page_permute=page_permute,
                                               page_transpose=page_transpose,
-                                              page_cast=page_cast)
+                                              page_cast=page_cast,
+                                              page_rotate=page_rotate)
         except ValueError:
-            if page_transpose is None and page_cast is None:
+            if page_transpose is None and page_cast is None and page_rotate is None:
                 return None
             raise  # as in load_layer
         except Exception:

@@ -334,6 +334,56 @@ class PageCast:
         return f"PageCast(scales={self.scales}, halves={self.halves})"
 
 
+class PageRotate:
+    """Read-side rotation of cached keys (docs/design.md, "rotated reads"): a
+    read delivers every page, [halves, T, heads, head_dim] bf16 with T implied
+    by the page size, with the rotary pairs of its K half (half 0) turned by
+    one angle per pair, which moves keys that carry RoPE for position p to
+    position p + delta. cos_sin is a float32 array [P, 2] of (cos, sin), P =
+    rot_dim / 2; rot_dim defaults to head_dim, and channels at or above it
+    are copied (partial rotary). style "neox" pairs channel i with i + P,
+    "gptj" pairs 2i with 2i + 1. V, the second half when halves == 2, is
+    copied. One table, hence one position delta, per request."""
+
+    STYLES = {"neox": 1, "gptj": 2}
+    __slots__ = ("heads", "head_dim", "rot_dim", "style", "halves", "cos_sin")
+
+    def __init__(self, heads: int, head_dim: int, cos_sin, rot_dim: Optional[int] = None,
+                 style: str = "neox", halves: int = 2):
+        if style not in self.STYLES:
+            raise ValueError(f"PageRotate.style is one of {tuple(self.STYLES)}")
+        self.heads, self.head_dim, self.halves = int(heads), int(head_dim), int(halves)
+        self.rot_dim = self.head_dim if rot_dim is None else int(rot_dim)
+        self.style = style
+        self.cos_sin = np.ascontiguousarray(cos_sin, dtype=np.float32)
+        if self.cos_sin.ndim != 2 or self.cos_sin.shape[1] != 2:
+            raise ValueError("PageRotate.cos_sin is a [rot_dim / 2, 2] array of (cos, sin)")
+        if self.cos_sin.shape[0] * 2 != self.rot_dim:
+            raise ValueError("PageRotate.cos_sin has one (cos, sin) row per pair, rot_dim / 2")
+
+    @classmethod
+    def from_delta(cls, delta, heads: int, head_dim: int, theta: float = 10000.0,
+                   rot_dim: Optional[int] = None, style: str = "neox", halves: int = 2):
+        """The table that moves keys by `delta` positions: pair i turns by
+        delta * theta ** (-2i / rot_dim), computed in float64 and rounded to
+        float32."""
+        rd = int(head_dim if rot_dim is None else rot_dim)
+        i = np.arange(rd // 2, dtype=np.float64)
+        ang = np.float64(delta) * np.float64(theta) ** (-2.0 * i / rd)
+        return cls(heads, head_dim, np.stack([np.cos(ang), np.sin(ang)], axis=1), rd, style,
+                   halves)
+
+    def wire(self):
+        """What the native calls take: (style, halves, heads, head_dim,
+        rot_dim, float32 table)."""
+        return (self.STYLES[self.style], self.halves, self.heads, self.head_dim, self.rot_dim,
+                self.cos_sin.reshape(-1))
+
+    def __repr__(self):
+        return (f"PageRotate(heads={self.heads}, head_dim={self.head_dim}, "
+                f"rot_dim={self.rot_dim}, style={self.style!r}, halves={self.halves})")
+
+
 class TensorSet:
     """A registered tensor set (InfinityConnection.register_tensor_set): the
     server-side id and the tensors, which it keeps alive."""
@@ -660,6 +710,64 @@ class InfinityConnection:
             raise Exception(f"Failed to {what} infinistore, ret = {ret}")
         return ticket
 
+    def _rotate_arg(self, page_rotate, cache, offsets, page_size: int, segments: int,
+                    segment_stride: int, page_slice=None, tensor_set=None, page_permute=None,
+                    page_transpose=None, page_cast=None):
+        """Refuse (ValueError) a rotated read the store cannot serve, before
+        anything is sent; the geometry rule is the native rotate_legal under
+        plain rules (the server judges every entry against its own codec).
+        Returns what the native calls take, PageRotate.wire()."""
+        if (page_slice is not None or tensor_set is not None or page_permute is not None
+                or page_transpose is not None or page_cast is not None):
+            raise ValueError("page_rotate cannot be combined with page_slice, tensor_set, "
+                             "page_permute, page_transpose or page_cast")
+        if not self.local_connected:
+            raise ValueError("rotated reads use the local GPU path")
+        if not isinstance(page_rotate, PageRotate):
+            raise ValueError("page_rotate must be a PageRotate")
+        if cache.dtype != torch.bfloat16:
+            raise ValueError("page_rotate needs a torch.bfloat16 cache")
+        if not 0 < page_size < 1 << 60 or not 0 < segments < 1 << 32 or segment_stride < 0:
+            raise ValueError("page_size and segments must be positive")
+        rot = page_rotate.wire()
+        if not _native._dbg_rotate_legal(0, page_size * 2, rot, segments, segment_stride * 2):
+            raise ValueError(
+                "illegal page rotation: halves is 1 or 2; head_dim is a multiple of 8 and "
+                "rot_dim <= head_dim an even number of at most "
+                f"{2 * _native._MAX_ROTATE_PAIRS} channels, rot_dim / 2 a multiple of 8 "
+                "(neox) or rot_dim a multiple of 8 (gptj); page_size is a multiple of halves * "
+                "heads * head_dim; segments hold whole (token, head) rows with a "
+                "segment_stride of a multiple of 8 elements; the table is finite")
+        offs = np.asarray(offsets, dtype=np.uint64)
+        if cache.data_ptr() % 16 != 0 or (offs % np.uint64(8)).any():
+            raise ValueError("rotated reads need a 16-byte-aligned cache and page offsets")
+        if len(offs) and (int(offs.max()) + (segments - 1) * segment_stride
+                          + page_size // segments > cache.numel()):
+            raise ValueError("a rotated page extends outside the tensor")
+        return rot
+
+    def _read_rotated(self, cache, keys, offsets, page_size, segments, segment_stride, rot,
+                      ticketed=False):
+        """One rotated read. Returns the ticket (0 unless ticketed)."""
+        offs = np.asarray(offsets, dtype=np.uint64)
+        args = (2, page_size * 2, cache.data_ptr(), _remap_device_id(cache))
+        ticket = 0
+        if ticketed:
+            if not isinstance(keys, (bytes, bytearray, memoryview)):
+                keys = self.pack_keys(keys)
+            ret, ticket = self.conn.rw_local_blob_async(
+                self.OP_R, keys, offs, *args, segments, segment_stride, None, None, None, None,
+                rot)
+        elif isinstance(keys, (bytes, bytearray, memoryview)):
+            ret = self.conn.rw_local_blob(self.OP_R, keys, offs, *args, False, 0, segments,
+                                          segment_stride, None, None, None, None, rot)
+        else:
+            ret = self.conn.rw_local_keys(self.OP_R, keys, offs, *args, False, 0, segments,
+                                          segment_stride, None, None, None, None, rot)
+        if ret < 0:
+            raise Exception(f"Failed to read from infinistore, ret = {ret}")
+        return ticket
+
     @staticmethod
     def _slice_arg(page_slice):
         """The native (n_pieces, page, offset, piece, stride) tuple, or None."""
@@ -924,7 +1032,8 @@ class InfinityConnection:
                    page_slice: Optional[PageSlice] = None, tensor_set=None,
                    page_permute: Optional[PagePermute] = None,
                    page_transpose: Optional[PageTranspose] = None,
-                   page_cast: Optional[PageCast] = None):
+                   page_cast: Optional[PageCast] = None,
+                   page_rotate: Optional[PageRotate] = None):
         """segments / segment_stride: scatter each page into that many equal
         pieces of `cache` (see write_pages), however the page was written.
         Local path only.
@@ -958,7 +1067,26 @@ class InfinityConnection:
         decoded to bf16 as for a bf16 reader, then divided by its half's scale
         and rounded to e4m3fn (saturating at +-448). page_size must be the
         written one. Not together with page_slice, tensor_set, page_permute
-        or page_transpose."""
+        or page_transpose.
+
+        page_rotate: deliver each bf16 page with the rotary pairs of its K
+        half turned by the given table (see PageRotate), however it was
+        written (plain, fp8 or mxfp4): the stored element is decoded to bf16
+        as for any reader, rotated in float32 and rounded to bf16 once.
+        page_size must be the written one. Works with segments (kv-major
+        caches); local path only, bf16 only, 16-byte-aligned cache and
+        offsets; not together with page_slice, tensor_set, page_permute,
+        page_transpose or page_cast; anything the server would refuse is a
+        ValueError before anything is sent."""
+        if page_rotate is not None:
+            segments = 1 if segments is None else segments
+            if tensor_set is None:
+                self._verify(cache)
+            rot = self._rotate_arg(page_rotate, cache, offsets, page_size, segments,
+                                   segment_stride, page_slice, tensor_set, page_permute,
+                                   page_transpose, page_cast)
+            self._read_rotated(cache, keys, offsets, page_size, segments, segment_stride, rot)
+            return
         if page_cast is not None:
             segments = 1 if segments is None else segments
             if tensor_set is None:
@@ -1034,14 +1162,24 @@ class InfinityConnection:
                          page_slice: Optional[PageSlice] = None, tensor_set=None,
                          page_permute: Optional[PagePermute] = None,
                          page_transpose: Optional[PageTranspose] = None,
-                         page_cast: Optional[PageCast] = None):
+                         page_cast: Optional[PageCast] = None,
+                         page_rotate: Optional[PageRotate] = None):
         """Ticketed read (local path, shm ring): pushes the request and
         returns a ticket; call wait_read(ticket) before using the data. Lets
         an engine overlap its own work (or further requests) with the copy —
         e.g. prefetching the next sequence's KV pages while decoding. Falls
         back to a blocking read (ticket 0) when the ring is unavailable.
         segments / segment_stride / page_slice / tensor_set / page_permute /
-        page_transpose / page_cast as in read_pages."""
+        page_transpose / page_cast / page_rotate as in read_pages."""
+        if page_rotate is not None:
+            segments = 1 if segments is None else segments
+            if tensor_set is None:
+                self._verify(cache)
+            rot = self._rotate_arg(page_rotate, cache, offsets, page_size, segments,
+                                   segment_stride, page_slice, tensor_set, page_permute,
+                                   page_transpose, page_cast)
+            return self._read_rotated(cache, keys, offsets, page_size, segments,
+                                      segment_stride, rot, ticketed=True)
         if page_cast is not None:
             segments = 1 if segments is None else segments
             if tensor_set is None:
