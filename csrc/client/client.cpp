@@ -405,9 +405,15 @@ int ClientConn::rw_local_packed(char op, const char* keys_blob, size_t blob_len,
                                 const PackedLocalPermExt* perm,
                                 const PackedLocalXposeExt* xpose,
                                 const PackedLocalCastExt* cast,
-                                const PackedLocalRotExt* rot, const float* rot_table) {
+                                const PackedLocalRotExt* rot, const float* rot_table,
+                                const PackedLocalShufExt* shuf) {
     if (out_ticket) *out_ticket = 0;  // 0 = completed synchronously
     if (!connected_) return -1;
+    if (shuf && shuf->tokens != 0 &&
+        ((slice && slice->n_pieces != 0) || tset || (perm && perm->rows != 0) ||
+         (xpose && xpose->tokens != 0) || (cast && cast->elem_type != 0) ||
+         (rot && rot->style != 0)))
+        return -INVALID_REQ;  // not together
     if (perm && perm->rows != 0 && ((slice && slice->n_pieces != 0) || tset))
         return -INVALID_REQ;  // not together
     if (xpose && xpose->tokens != 0 &&
@@ -477,7 +483,7 @@ int ClientConn::rw_local_packed(char op, const char* keys_blob, size_t blob_len,
 
     std::vector<uint8_t> body =
         build_packed_local(h, n_segments, segment_stride, offsets, keys_blob, blob_len, slice,
-                           tset, perm, xpose, cast, rot, rot_table);
+                           tset, perm, xpose, cast, rot, rot_table, shuf);
 
     char wire_op = (op == 'W') ? OP_W_FAST : OP_R_FAST;
     static const bool dbg = getenv("IFS_CLIENT_DEBUG") != nullptr;

@@ -81,7 +81,12 @@ class ClientConn {
                         const PackedLocalXposeExt* xpose = nullptr,
                         const PackedLocalCastExt* cast = nullptr,
                         const PackedLocalRotExt* rot = nullptr,
-                        const float* rot_table = nullptr);
+                        const float* rot_table = nullptr,
+                        const PackedLocalShufExt* shuf = nullptr);
+    // shuf (null or tokens == 0: not shuffled): the tensor holds every page as
+    // a shuffled cache block (shuffled pages, core/page_codec.h). With a
+    // slice, a tensor set, a permutation, a transpose, a cast or a rotation as
+    // well it returns -INVALID_REQ without sending anything.
     // rot (null or style == 0: not rotated) with rot_table, rot->rot_dim
     // (cos, sin) floats: a READ turns the K half of every bf16 page while it
     // loads (rotated reads, core/page_codec.h). On a write, or with a slice, a

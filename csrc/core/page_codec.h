@@ -467,4 +467,62 @@ inline PageRotate rotate_from_wire(const PackedLocalRotExt& e, const float* tabl
     return {e.style, e.halves, e.heads, e.head_dim, e.rot_dim, table};
 }
 
+// Shuffled pages (docs/design.md, "shuffled pages"): on the CLIENT side of a
+// request a page may be the shuffled cache block that assembly paged-attention
+// kernels read. A page is outer (1 or 2) halves of tokens x heads x cols
+// elements of elem_bytes; with T, H, C those extents and X = 16 / elem_bytes,
+// element (o, t, h, c) sits at element ((o*T + t)*H + h)*C + c of the STORED
+// (canonical) page and, on the client, in tile o*H + h of T*C elements at
+//     form 1 (K, [C/X, T, X]):  ((c/X)*T + t)*X + c%X
+//     form 2 (V, [T/X, C, X]):  ((t/X)*C + c)*X + t%X
+// to which PageSegments then apply as to any page. A SQUARE is X tokens x X
+// channels: X 16-byte units of X consecutive stored rows, and X*16 contiguous
+// client bytes, held as they are under form 1 and transposed under form 2.
+
+// Client-side element order of a request's pages; tokens == 0 (the default)
+// is "not shuffled". form[o] is half o's form; a one-half page uses form[0].
+struct PageShuffle {
+    uint32_t outer = 0, tokens = 0, heads = 0, cols = 0, elem_bytes = 0;
+    uint32_t form[2] = {0, 0};
+};
+
+inline bool shuffle_is_set(const PageShuffle& x) { return x.tokens != 0; }
+
+// The one predicate for a shuffled page (wire parser, server, shard,
+// launchers, bindings, Python client). Whole squares tile every (half, head)
+// tile; under a transforming codec the elements are bf16 and, for mxfp4, a
+// (token, head) row is whole 32-element groups, so a group never leaves its
+// row. Both forms are judged whatever outer is. The two bounds are conditions,
+// not tuning values: the kernels count the squares of a tile and the tiles of
+// a page in 32 bits. A tile never straddles a client segment, and the page
+// obeys segments_legal like any other. There is no bound on the tile's size.
+inline bool shuffle_legal(PageCodec c, size_t page_bytes, const PageShuffle& x,
+                          const PageSegments& seg = {}) {
+    if (x.outer < 1 || x.outer > 2 || x.tokens < 1 || x.heads < 1 || x.cols < 1) return false;
+    if (x.elem_bytes != 1 && x.elem_bytes != 2 && x.elem_bytes != 4) return false;
+    if (page_codec_transforms(c) && x.elem_bytes != kPageElemBytes) return false;
+    for (uint32_t f : x.form)
+        if (f != 1 && f != 2) return false;
+    const uint32_t X = 16 / x.elem_bytes;
+    if (x.tokens % X != 0 || x.cols % X != 0) return false;
+    if (c == PageCodec::kMxfp4 && x.cols % 32 != 0) return false;
+    // 128-bit products: five 32-bit values off the wire must not wrap into a match.
+    using u128 = unsigned __int128;
+    if (static_cast<u128>(x.outer) * x.tokens * x.heads * x.cols * x.elem_bytes !=
+        static_cast<u128>(page_bytes))
+        return false;
+    if (static_cast<uint64_t>(x.tokens / X) * (x.cols / X) > 0xffffffffull) return false;
+    if (static_cast<uint64_t>(x.outer) * x.heads > 0xffffffffull) return false;
+    if (seg.n == 0 || (static_cast<uint64_t>(x.outer) * x.heads) % seg.n != 0) return false;
+    return segments_legal(c, page_bytes, seg.n, seg.stride_bytes);
+}
+
+// The geometry as the wire extension carries it, and back.
+inline PackedLocalShufExt shuffle_to_wire(const PageShuffle& x) {
+    return {x.outer, x.tokens, x.heads, x.cols, x.elem_bytes, x.form[0], x.form[1], 0};
+}
+inline PageShuffle shuffle_from_wire(const PackedLocalShufExt& e) {
+    return {e.outer, e.tokens, e.heads, e.cols, e.elem_bytes, {e.form_k, e.form_v}};
+}
+
 }  // namespace ifs

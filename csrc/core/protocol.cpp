@@ -166,7 +166,8 @@ std::vector<uint8_t> build_packed_local(PackedLocalHdr h, uint32_t n_segments,
                                         const PackedLocalPermExt* perm,
                                         const PackedLocalXposeExt* xpose,
                                         const PackedLocalCastExt* cast,
-                                        const PackedLocalRotExt* rot, const float* rot_table) {
+                                        const PackedLocalRotExt* rot, const float* rot_table,
+                                        const PackedLocalShufExt* shuf) {
     const size_t n = h.n_blocks;
     const bool seg = n_segments != 1;
     const bool sliced = slice && slice->n_pieces != 0;
@@ -188,7 +189,10 @@ std::vector<uint8_t> build_packed_local(PackedLocalHdr h, uint32_t n_segments,
     const bool rotated = rot && rot->style != 0;
     if (rotated) h.flags |= kLocalFlagRotated;
     const size_t table_bytes = rotated ? static_cast<size_t>(rot->rot_dim) * sizeof(float) : 0;
-    const size_t ext = cast_end + (rotated ? sizeof(PackedLocalRotExt) + table_bytes : 0);
+    const size_t rot_end = cast_end + (rotated ? sizeof(PackedLocalRotExt) + table_bytes : 0);
+    const bool shuffled = shuf && shuf->tokens != 0;
+    if (shuffled) h.flags |= kLocalFlagShuffled;
+    const size_t ext = rot_end + (shuffled ? sizeof(PackedLocalShufExt) : 0);
     std::vector<uint8_t> body(sizeof(h) + ext + n * 8 + blob_len);
     memcpy(body.data(), &h, sizeof(h));
     if (seg) {
@@ -205,6 +209,7 @@ std::vector<uint8_t> build_packed_local(PackedLocalHdr h, uint32_t n_segments,
         if (table_bytes)
             memcpy(body.data() + sizeof(h) + cast_end + sizeof(*rot), rot_table, table_bytes);
     }
+    if (shuffled) memcpy(body.data() + sizeof(h) + rot_end, shuf, sizeof(*shuf));
     if (n) memcpy(body.data() + sizeof(h) + ext, offsets, n * 8);
     if (blob_len) memcpy(body.data() + sizeof(h) + ext + n * 8, keys_blob, blob_len);
     return body;
@@ -237,6 +242,11 @@ bool parse_packed_local(char op, const uint8_t* body, size_t body_len, PackedLoc
     if (rotated && (op != OP_R_FAST ||
                     (h.flags & (kLocalFlagSliced | kLocalFlagTensorSet | kLocalFlagPermuted |
                                 kLocalFlagTransposed | kLocalFlagCast))))
+        return false;
+    // A shuffled page stands next to none of the other geometries.
+    const bool shuffled = (h.flags & kLocalFlagShuffled) != 0;
+    if (shuffled && (h.flags & (kLocalFlagSliced | kLocalFlagTensorSet | kLocalFlagPermuted |
+                                kLocalFlagTransposed | kLocalFlagCast | kLocalFlagRotated)))
         return false;
     if (h.flags & kLocalFlagSegmented) {
         if (body_len < pos + sizeof(PackedLocalSegExt)) return false;
@@ -352,6 +362,22 @@ bool parse_packed_local(char op, const uint8_t* body, size_t body_len, PackedLoc
                           PageSegments{out->n_segments, out->segment_stride}))
             return false;
         out->rot = e;
+    }
+    out->shuf = PackedLocalShufExt{};
+    if (shuffled) {
+        if (body_len < pos + sizeof(PackedLocalShufExt)) return false;
+        PackedLocalShufExt e;
+        memcpy(&e, body + pos, sizeof(e));
+        pos += sizeof(e);
+        if (e.rsvd != 0) return false;
+        PageCodec codec = PageCodec::kNone;
+        if (op == OP_W_FAST && !page_codec_from_flags(h.flags, &codec)) return false;
+        // tokens == 0 fails shuffle_legal: a parsed request is shuffled
+        // exactly when tokens != 0.
+        if (!shuffle_legal(codec, h.block_size, shuffle_from_wire(e),
+                           PageSegments{out->n_segments, out->segment_stride}))
+            return false;
+        out->shuf = e;
     }
     const size_t n = h.n_blocks;
     const size_t off_end = pos + n * 8;

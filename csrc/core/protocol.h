@@ -60,7 +60,8 @@ constexpr char OP_STATS = 'Q';    // server stats JSON over the wire (extension)
 // when kLocalFlagTensorSet is set,] [PackedLocalPermExt when
 // kLocalFlagPermuted is set,] [PackedLocalXposeExt when kLocalFlagTransposed
 // is set,] [PackedLocalCastExt when kLocalFlagCast is set,] [PackedLocalRotExt
-// and its rot_dim float32 table when kLocalFlagRotated is set,] u64 offsets[n],
+// and its rot_dim float32 table when kLocalFlagRotated is set,]
+// [PackedLocalShufExt when kLocalFlagShuffled is set,] u64 offsets[n],
 // NUL-separated key bytes (n keys).
 constexpr char OP_W_FAST = 'w';
 constexpr char OP_R_FAST = 'r';
@@ -195,6 +196,23 @@ struct PackedLocalRotExt {
 #pragma pack(pop)
 static_assert(sizeof(PackedLocalRotExt) == 24, "packed local rotate extension size");
 
+// Follows PackedLocalHdr and every other extension when kLocalFlagShuffled is
+// set: the element order of the request's pages in CLIENT memory
+// (core/page_codec.h, PageShuffle; docs/design.md, "shuffled pages").
+#pragma pack(push, 1)
+struct PackedLocalShufExt {
+    uint32_t outer;
+    uint32_t tokens;
+    uint32_t heads;
+    uint32_t cols;
+    uint32_t elem_bytes;
+    uint32_t form_k;  // form of half 0: 1 (K form) or 2 (V form)
+    uint32_t form_v;  // form of half 1
+    uint32_t rsvd;    // 0
+};
+#pragma pack(pop)
+static_assert(sizeof(PackedLocalShufExt) == 32, "packed local shuffle extension size");
+
 // OP_TSET_REGISTER body: this header, then n_tensors records in set order.
 #pragma pack(push, 1)
 struct PackedTensorSetHdr {
@@ -264,6 +282,13 @@ constexpr uint32_t kLocalFlagCast = 256;
 // kLocalFlagPermuted, kLocalFlagTransposed or kLocalFlagCast it is
 // INVALID_REQ.
 constexpr uint32_t kLocalFlagRotated = 512;
+// The client holds each page as a shuffled cache block (per head, K as
+// [cols/X, tokens, X] and V as [tokens/X, cols, X], X = 16 / elem_bytes), as
+// the PackedLocalShufExt after all other extensions says (extension; both
+// packed ops). The stored block is the canonical page's. Together with
+// kLocalFlagSliced, kLocalFlagTensorSet, kLocalFlagPermuted,
+// kLocalFlagTransposed, kLocalFlagCast or kLocalFlagRotated it is INVALID_REQ.
+constexpr uint32_t kLocalFlagShuffled = 1024;
 
 std::string op_name(char op);
 
@@ -345,7 +370,10 @@ std::vector<uint8_t> build_packed_local(PackedLocalHdr h, uint32_t n_segments,
                                         const PackedLocalXposeExt* xpose = nullptr,
                                         const PackedLocalCastExt* cast = nullptr,
                                         const PackedLocalRotExt* rot = nullptr,
-                                        const float* rot_table = nullptr);
+                                        const float* rot_table = nullptr,
+                                        const PackedLocalShufExt* shuf = nullptr);
+// (The shuffle extension and kLocalFlagShuffled are written only for a `shuf`
+// with tokens != 0, its rsvd as given.)
 // (The rotate extension, the rot_dim floats at rot_table and kLocalFlagRotated
 // are written only for a `rot` with style != 0, its rsvd as given.)
 // (The cast extension and kLocalFlagCast are written only for a `cast` with
@@ -379,6 +407,7 @@ struct PackedLocalReq {
     PackedLocalCastExt cast{};    // elem_type == 0: not cast
     PackedLocalRotExt rot{};      // style == 0: not rotated
     std::vector<float> rot_table;  // rot.rot_dim values when rotated
+    PackedLocalShufExt shuf{};     // tokens == 0: not shuffled
     std::vector<std::pair<std::string_view, uint64_t>> blocks;
 };
 // False (the server answers INVALID_REQ) for a truncated body or extension,
@@ -400,7 +429,9 @@ struct PackedLocalReq {
 // judges in place of segments_legal. kLocalFlagRotated is refused on
 // OP_W_FAST, next to any of those five flags, with a cut table, and when
 // rotate_legal refuses the geometry or the table for block_size and the
-// segments under plain rules.
+// segments under plain rules. kLocalFlagShuffled is refused next to any of
+// those six flags, and when shuffle_legal refuses the geometry for block_size
+// (same codec choice as for segments).
 bool parse_packed_local(char op, const uint8_t* body, size_t body_len, PackedLocalReq* out);
 
 // Sentinel for duplicate-key allocations: the server returns rkey=0, addr=0

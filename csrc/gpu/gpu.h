@@ -312,6 +312,32 @@ bool launch_load_rotated(int dev, Stream s, PageCodec codec, const uint64_t* dev
 // Workgroup size of the rotate kernels, a (block, segment, chunk) each.
 constexpr int kRotateThreads = 256;
 
+// --- shuffled pages (csrc/gpu/shuffle.hip) --------------------------------------
+// The CLIENT side of every page (source of kStore, destination of kLoad) is a
+// shuffled cache block (core/page_codec.h, PageShuffle; docs/design.md,
+// "shuffled pages"), split into seg.n segments on top of that when seg.n > 1;
+// the stored block is byte-identical to the one the contiguous kernels make of
+// the canonical page. One lane moves one square of X tokens x X channels with
+// X 16-byte accesses on each side and transposes it in registers for form 2;
+// a workgroup is a (block, chunk) over the page's squares. There is no byte
+// fallback: false before any launch, with last_error() set, for a geometry
+// shuffle_legal refuses, unless aligned16 holds (every descriptor pointer is a
+// multiple of 16; the CALLER checks), for a segment stride that is applied and
+// is not a multiple of 16, or for a page or a grid that does not fit 31 bits
+// of squares or workgroups.
+bool launch_copy_blocks_shuf(int dev, Stream s, const uint64_t* dev_src, const uint64_t* dev_dst,
+                             int n_blocks, size_t bytes_per_block, bool aligned16,
+                             PageSegments seg, PageDir dir, PageShuffle sh);
+// Transforming codecs (bf16 pages), scales as for launch_transform_blocks: fp8
+// keeps ONE scale per page, mxfp4 indexes codes and scale bytes by the
+// page-global STORED unit.
+bool launch_transform_blocks_shuf(int dev, Stream s, PageCodec codec, PageDir dir,
+                                  const uint64_t* dev_src, const uint64_t* dev_dst,
+                                  float* dev_scales, int n_blocks, size_t elems_per_block,
+                                  bool aligned16, PageSegments seg, PageShuffle sh);
+// Workgroup size of the shuffle kernels: one square per lane and sweep.
+constexpr int kShufThreads = 256;
+
 // --- block fingerprint ------------------------------------------------------
 // 64-bit position-salted fingerprint per block -> out_hashes[i] (device mem).
 bool launch_hash_blocks(int dev, Stream s, const uint64_t* dev_ptrs, int n_blocks,

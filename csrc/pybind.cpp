@@ -714,6 +714,82 @@ std::pair<bool, std::vector<float>> transform_blocks_cast_py(
     return {ok, scales};
 }
 
+// ---- shuffled pages (docs/design.md, "shuffled pages") -------------------------
+// A shuffle from Python: None, or (outer, tokens, heads, cols, elem_bytes,
+// form_k, form_v), the extents in elements.
+PageShuffle shuf_from_py(const char* what, const py::object& o) {
+    PageShuffle sh;
+    if (o.is_none()) return sh;
+    py::tuple t = o.cast<py::tuple>();
+    if (t.size() != 7)
+        throw std::invalid_argument(std::string(what) + ": a shuffle is (outer, tokens, heads, "
+                                                        "cols, elem_bytes, form_k, form_v)");
+    sh.outer = t[0].cast<uint32_t>();
+    sh.tokens = t[1].cast<uint32_t>();
+    sh.heads = t[2].cast<uint32_t>();
+    sh.cols = t[3].cast<uint32_t>();
+    sh.elem_bytes = t[4].cast<uint32_t>();
+    sh.form[0] = t[5].cast<uint32_t>();
+    sh.form[1] = t[6].cast<uint32_t>();
+    return sh;
+}
+
+// The two shuffle launchers, called directly as the transposed ones are: one
+// client page pointer and one pool pointer per block; a refusal is False.
+bool copy_blocks_shuf_py(const std::vector<uint64_t>& client, const std::vector<uint64_t>& pool,
+                         size_t bytes_per_block, const py::object& shuffle, uint32_t n_segments,
+                         uint64_t segment_stride, bool to_pool, int device) {
+    const char* what = "_dbg_copy_blocks_shuf";
+    const PageShuffle sh = shuf_from_py(what, shuffle);
+    require_gpu_and_pairs(what, client, pool);
+    size_t n = client.size();
+    py::gil_scoped_release rel;
+    Pinned<uint64_t> h_client(n ? n : 1), h_pool(n ? n : 1);
+    memcpy(h_client.p, client.data(), n * 8);
+    memcpy(h_pool.p, pool.data(), n * 8);
+    ScopedStream st(device);
+    bool ok = gpu::launch_copy_blocks_shuf(
+        device, st.s, to_pool ? h_client.p : h_pool.p, to_pool ? h_pool.p : h_client.p,
+        static_cast<int>(n), bytes_per_block, all_aligned16(client, pool),
+        PageSegments{n_segments, segment_stride}, to_pool ? PageDir::kStore : PageDir::kLoad, sh);
+    // Always drain the stream before the pinned descriptors go away.
+    if (!gpu::stream_sync(st.s))
+        throw std::runtime_error(std::string(what) + " failed: " + gpu::last_error());
+    return ok;
+}
+
+// to_pool quantizes (the scales come back), else dequantizes (they go in).
+std::pair<bool, std::vector<float>> transform_blocks_shuf_py(
+    int codec_id, bool to_pool, const std::vector<uint64_t>& client,
+    const std::vector<uint64_t>& pool, std::vector<float> scales, size_t elems_per_block,
+    const py::object& shuffle, uint32_t n_segments, uint64_t segment_stride, int device) {
+    const char* what = "_dbg_transform_blocks_shuf";
+    const PageCodec codec = codec_from_id(what, codec_id);
+    const PageShuffle sh = shuf_from_py(what, shuffle);
+    require_gpu_and_pairs(what, client, pool);
+    size_t n = client.size();
+    const bool page_scale = page_codec_info(codec).page_scale;
+    if (page_scale && !to_pool && scales.size() != n)
+        throw std::invalid_argument(std::string(what) + ": one scale per block");
+    scales.resize(page_scale ? n : 0);
+    py::gil_scoped_release rel;
+    Pinned<uint64_t> h_client(n ? n : 1), h_pool(n ? n : 1);
+    Pinned<float> h_scale(n ? n : 1);
+    memcpy(h_client.p, client.data(), n * 8);
+    memcpy(h_pool.p, pool.data(), n * 8);
+    memcpy(h_scale.p, scales.data(), scales.size() * sizeof(float));
+    ScopedStream st(device);
+    bool ok = gpu::launch_transform_blocks_shuf(
+        device, st.s, codec, to_pool ? PageDir::kStore : PageDir::kLoad,
+        to_pool ? h_client.p : h_pool.p, to_pool ? h_pool.p : h_client.p, h_scale.p,
+        static_cast<int>(n), elems_per_block, all_aligned16(client, pool),
+        PageSegments{n_segments, segment_stride}, sh);
+    if (!gpu::stream_sync(st.s))
+        throw std::runtime_error(std::string(what) + " failed: " + gpu::last_error());
+    if (ok) memcpy(scales.data(), h_scale.p, scales.size() * sizeof(float));
+    return {ok, scales};
+}
+
 // ---- rotated reads (docs/design.md, "rotated reads") ---------------------------
 // A rotation from Python: None, or (style, halves, heads, head_dim, rot_dim,
 // table), the table a float32 buffer of rot_dim values, (cos, sin) per pair.
@@ -1146,7 +1222,11 @@ PYBIND11_MODULE(_native, m) {
                bool sync_response, uint32_t extra_flags, uint32_t n_segments,
                uint64_t segment_stride, const py::object& page_slice,
                const py::object& page_permute, const py::object& page_transpose,
-               const py::object& page_cast, const py::object& page_rotate) {
+               const py::object& page_cast, const py::object& page_rotate,
+               const py::object& page_shuffle) {
+                // page_shuffle: None or shuf_from_py's tuple of 7
+                const PackedLocalShufExt se =
+                    shuffle_to_wire(shuf_from_py("rw_local", page_shuffle));
                 // page_rotate: None or rotate_from_py's tuple of 6; reads only
                 RotatePy rp;
                 rotate_from_py("rw_local", page_rotate, &rp);
@@ -1188,7 +1268,7 @@ PYBIND11_MODULE(_native, m) {
                                          byte_offs.data(), n, block_size, ptr, device,
                                          sync_response, nullptr, extra_flags, n_segments,
                                          segment_stride * element_size, &sl, nullptr, &pe, &xe,
-                                         &ce, &re, rp.table.data());
+                                         &ce, &re, rp.table.data(), &se);
             },
             py::arg("op"), py::arg("keys"), py::arg("offsets"), py::arg("element_size"),
             py::arg("block_size"), py::arg("ptr"), py::arg("device"),
@@ -1196,7 +1276,7 @@ PYBIND11_MODULE(_native, m) {
             py::arg("n_segments") = 1, py::arg("segment_stride") = 0,
             py::arg("page_slice") = py::none(), py::arg("page_permute") = py::none(),
             py::arg("page_transpose") = py::none(), py::arg("page_cast") = py::none(),
-            py::arg("page_rotate") = py::none())
+            py::arg("page_rotate") = py::none(), py::arg("page_shuffle") = py::none())
         .def(
             "rw_local_blob",
             [](ClientConn& c, const std::string& op, py::buffer blob, py::buffer offsets,
@@ -1204,7 +1284,11 @@ PYBIND11_MODULE(_native, m) {
                bool sync_response, uint32_t extra_flags, uint32_t n_segments,
                uint64_t segment_stride, const py::object& page_slice,
                const py::object& page_permute, const py::object& page_transpose,
-               const py::object& page_cast, const py::object& page_rotate) {
+               const py::object& page_cast, const py::object& page_rotate,
+               const py::object& page_shuffle) {
+                // page_shuffle: None or shuf_from_py's tuple of 7
+                const PackedLocalShufExt se =
+                    shuffle_to_wire(shuf_from_py("rw_local", page_shuffle));
                 // page_rotate: None or rotate_from_py's tuple of 6; reads only
                 RotatePy rp;
                 rotate_from_py("rw_local", page_rotate, &rp);
@@ -1239,7 +1323,7 @@ PYBIND11_MODULE(_native, m) {
                                          n, block_size, ptr, device, sync_response, nullptr,
                                          extra_flags, n_segments,
                                          segment_stride * element_size, &sl, nullptr, &pe, &xe,
-                                         &ce, &re, rp.table.data());
+                                         &ce, &re, rp.table.data(), &se);
             },
             py::arg("op"), py::arg("blob"), py::arg("offsets"), py::arg("element_size"),
             py::arg("block_size"), py::arg("ptr"), py::arg("device"),
@@ -1247,14 +1331,18 @@ PYBIND11_MODULE(_native, m) {
             py::arg("n_segments") = 1, py::arg("segment_stride") = 0,
             py::arg("page_slice") = py::none(), py::arg("page_permute") = py::none(),
             py::arg("page_transpose") = py::none(), py::arg("page_cast") = py::none(),
-            py::arg("page_rotate") = py::none())
+            py::arg("page_rotate") = py::none(), py::arg("page_shuffle") = py::none())
         .def(
             "rw_local_blob_async",
             [](ClientConn& c, const std::string& op, py::buffer blob, py::buffer offsets,
                uint64_t element_size, int block_size, uintptr_t ptr, int device,
                uint32_t n_segments, uint64_t segment_stride, const py::object& page_slice,
                const py::object& page_permute, const py::object& page_transpose,
-               const py::object& page_cast, const py::object& page_rotate) {
+               const py::object& page_cast, const py::object& page_rotate,
+               const py::object& page_shuffle) {
+                // page_shuffle: None or shuf_from_py's tuple of 7
+                const PackedLocalShufExt se =
+                    shuffle_to_wire(shuf_from_py("rw_local", page_shuffle));
                 RotatePy rp;
                 rotate_from_py("rw_local", page_rotate, &rp);
                 const PackedLocalRotExt re = rotate_to_wire(rp.r);
@@ -1286,7 +1374,7 @@ PYBIND11_MODULE(_native, m) {
                                             byte_offs.data(), n, block_size, ptr, device,
                                             /*sync_response=*/true, &ticket, 0, n_segments,
                                             segment_stride * element_size, &sl, nullptr,
-                                            &pe, &xe, &ce, &re, rp.table.data());
+                                            &pe, &xe, &ce, &re, rp.table.data(), &se);
                 }
                 return py::make_tuple(ret, ticket);
             },
@@ -1295,7 +1383,7 @@ PYBIND11_MODULE(_native, m) {
             py::arg("n_segments") = 1, py::arg("segment_stride") = 0,
             py::arg("page_slice") = py::none(), py::arg("page_permute") = py::none(),
             py::arg("page_transpose") = py::none(), py::arg("page_cast") = py::none(),
-            py::arg("page_rotate") = py::none())
+            py::arg("page_rotate") = py::none(), py::arg("page_shuffle") = py::none())
         .def(
             "rw_tset_blob",
             [](ClientConn& c, const std::string& op, py::buffer blob, py::buffer offsets,
@@ -1739,6 +1827,31 @@ PYBIND11_MODULE(_native, m) {
           py::arg("device"), py::arg("n_streams"), py::arg("slots_per_stream"),
           py::arg("max_descs_per_slot"), py::arg("copy_jobs"), py::arg("casts"),
           py::arg("n_threads"), py::arg("timeout_s"));
+    // The shuffle-geometry predicate; the shuffle is shuf_from_py's tuple of 7,
+    // the client segments as above.
+    m.def("_dbg_shuffle_legal",
+          [](int codec, size_t page_bytes, const py::object& shuffle, uint32_t n_segments,
+             uint64_t stride_bytes) {
+              if (shuffle.is_none())
+                  throw std::invalid_argument("_dbg_shuffle_legal: a shuffle is a tuple of 7");
+              return shuffle_legal(codec_from_id("_dbg_shuffle_legal", codec), page_bytes,
+                                   shuf_from_py("_dbg_shuffle_legal", shuffle),
+                                   PageSegments{n_segments, stride_bytes});
+          },
+          py::arg("codec"), py::arg("page_bytes"), py::arg("shuffle"), py::arg("n_segments") = 1,
+          py::arg("stride_bytes") = 0);
+    m.attr("_SHUF_THREADS") = gpu::kShufThreads;
+    // The shuffle launchers (gpu.h), called directly: one client page pointer
+    // and one pool pointer per block. Return False for what the launcher
+    // refuses; the transform form returns (ok, scales).
+    m.def("_dbg_copy_blocks_shuf", &copy_blocks_shuf_py, py::arg("client_ptrs"),
+          py::arg("pool_ptrs"), py::arg("bytes_per_block"), py::arg("shuffle"),
+          py::arg("n_segments") = 1, py::arg("segment_stride") = 0, py::arg("to_pool") = true,
+          py::arg("device") = 0);
+    m.def("_dbg_transform_blocks_shuf", &transform_blocks_shuf_py, py::arg("codec"),
+          py::arg("to_pool"), py::arg("client_ptrs"), py::arg("pool_ptrs"), py::arg("scales"),
+          py::arg("elems_per_block"), py::arg("shuffle"), py::arg("n_segments") = 1,
+          py::arg("segment_stride") = 0, py::arg("device") = 0);
     // The rotation predicate; the rotation is rotate_from_py's tuple of 6, the
     // client segments as above.
     m.def("_dbg_rotate_legal",
@@ -1817,7 +1930,20 @@ PYBIND11_MODULE(_native, m) {
              const std::vector<uint64_t>& offsets, const std::vector<std::string>& keys,
              uint32_t n_segments, uint64_t segment_stride, const py::object& slice,
              const py::object& tensor_set, const py::object& permute,
-             const py::object& transpose, const py::object& cast, const py::object& rotate) {
+             const py::object& transpose, const py::object& cast, const py::object& rotate,
+             const py::object& shuffle) {
+              // None, or shuf_from_py's tuple of 7, optionally with rsvd as an
+              // eighth value
+              PackedLocalShufExt se{};
+              if (!shuffle.is_none()) {
+                  py::tuple t = shuffle.cast<py::tuple>();
+                  if (t.size() != 7 && t.size() != 8)
+                      throw std::invalid_argument(
+                          "_dbg_build_packed_local: a shuffle is a tuple of 7 (or 8)");
+                  se = shuffle_to_wire(
+                      shuf_from_py("_dbg_build_packed_local", py::tuple(t[py::slice(0, 7, 1)])));
+                  if (t.size() == 8) se.rsvd = t[7].cast<uint32_t>();
+              }
               // None, or rotate_from_py's tuple of 6, optionally with rsvd as
               // a seventh value, written as given
               RotatePy rp;
@@ -1888,7 +2014,7 @@ PYBIND11_MODULE(_native, m) {
               auto v = build_packed_local(h, n_segments, segment_stride, offsets.data(),
                                           blob.data(), blob.size(), &sl,
                                           tensor_set.is_none() ? nullptr : &ts, &pe, &xe,
-                                          &ce, &re, rp.table.data());
+                                          &ce, &re, rp.table.data(), &se);
               return py::bytes(reinterpret_cast<const char*>(v.data()), v.size());
           },
           py::arg("device"), py::arg("pid"), py::arg("base_ptr"), py::arg("base_offset"),
@@ -1897,7 +2023,7 @@ PYBIND11_MODULE(_native, m) {
           py::arg("segment_stride") = 0, py::arg("slice") = py::none(),
           py::arg("tensor_set") = py::none(), py::arg("permute") = py::none(),
           py::arg("transpose") = py::none(), py::arg("cast") = py::none(),
-          py::arg("rotate") = py::none());
+          py::arg("rotate") = py::none(), py::arg("shuffle") = py::none());
     m.def("_dbg_parse_packed_local", [](const std::string& op, py::bytes data) {
         std::string s = data;
         PackedLocalReq r;
@@ -1953,6 +2079,12 @@ PYBIND11_MODULE(_native, m) {
                           r.rot_table.size() * sizeof(float)));
         else
             d["rotate"] = py::none();
+        // None, or the tuple of 7
+        if (r.shuf.tokens)
+            d["shuffle"] = py::make_tuple(r.shuf.outer, r.shuf.tokens, r.shuf.heads, r.shuf.cols,
+                                          r.shuf.elem_bytes, r.shuf.form_k, r.shuf.form_v);
+        else
+            d["shuffle"] = py::none();
         py::list offs, keys;
         for (auto& [key, off] : r.blocks) {
             offs.append(off);

@@ -549,6 +549,7 @@ bool parse_packed_local(char op, const uint8_t* body, size_t body_len, Server::L
     v->cast = cast_from_wire(req.cast);
     v->rot = rotate_from_wire(req.rot, nullptr);
     v->rot_table = std::move(req.rot_table);
+    v->shuf = shuffle_from_wire(req.shuf);
     v->ipc = body + offsetof(PackedLocalHdr, ipc);
     v->ipc_len = 64;
     v->blocks = std::move(req.blocks);
@@ -851,14 +852,20 @@ void Server::op_local_write(Conn* c, const LocalView& msg, const ReqCtx& ctx) {
         (tset || permuted || !transpose_legal(codec, page, msg.xpose,
                                               PageSegments{msg.n_segments, msg.segment_stride})))
         return reply_local(c, ctx, INVALID_REQ);
+    // Shuffled source pages: likewise, and next to none of the others.
+    const bool shuffled = shuffle_is_set(msg.shuf);
+    if (shuffled &&
+        (tset || permuted || transposed || is_cast ||
+         !shuffle_legal(codec, page, msg.shuf, PageSegments{msg.n_segments, msg.segment_stride})))
+        return reply_local(c, ctx, INVALID_REQ);
     // The quantize kernels load 16 bytes per lane: every source page must
     // start 16-byte aligned (pool blocks always do), and a 16-byte stride
     // then keeps every segment aligned.
-    // The transpose kernels move 16 bytes per lane for every codec.
-    if (transposed && msg.n_segments != 1 && msg.segment_stride % 16 != 0)
+    // The transpose and shuffle kernels move 16 bytes per lane for every codec.
+    if ((transposed || shuffled) && msg.n_segments != 1 && msg.segment_stride % 16 != 0)
         return reply_local(c, ctx, INVALID_REQ);
     // So do the cast kernels (8 bytes per lane on the client, 16 in the pool).
-    if ((page_codec_transforms(codec) || transposed || is_cast) && !tset) {
+    if ((page_codec_transforms(codec) || transposed || is_cast || shuffled) && !tset) {
         for (size_t i = 0; i < nb; i++)
             if ((client_addr + msg.blocks[i].second) % 16 != 0)
                 return reply_local(c, ctx, INVALID_REQ);
@@ -941,6 +948,7 @@ void Server::op_local_write(Conn* c, const LocalView& msg, const ReqCtx& ctx) {
     job.perm = msg.perm;
     job.xpose = msg.xpose;
     job.cast = msg.cast;
+    job.shuf = msg.shuf;
     job.scales = scales_out;
     for (size_t i = 0; i < n_fresh; i++) {
         auto* e = slab_batch.make();
@@ -1121,6 +1129,12 @@ void Server::op_local_read(Conn* c, const LocalView& msg, const ReqCtx& ctx) {
                     msg.rot_table.size() != rot.rot_dim ||
                     !rotate_legal(PageCodec::kNone, page, rot, client_seg)))
         return reply_local(c, ctx, INVALID_REQ);
+    // Shuffled read: as a transposed one, next to none of the others.
+    const bool shuffled = shuffle_is_set(msg.shuf);
+    if (shuffled && (sliced || tset || permuted || transposed || is_cast || rotated ||
+                     !shuffle_legal(PageCodec::kNone, page, msg.shuf, client_seg) ||
+                     (msg.n_segments != 1 && msg.segment_stride % 16 != 0)))
+        return reply_local(c, ctx, INVALID_REQ);
 
     auto tr0 = Clock::now();
     // Group blocks by the shard whose GPU EXECUTES the copy. For same-GPU
@@ -1224,6 +1238,17 @@ void Server::op_local_read(Conn* c, const LocalView& msg, const ReqCtx& ctx) {
                     err = INVALID_REQ;
                     return false;
                 }
+            } else if (shuffled) {
+                // As for a transpose: the written size for every codec
+                // (plain entries included), the geometry legal for the
+                // entry's codec, and a 16-byte-aligned client address,
+                // because the shuffle kernels have no byte path.
+                if (!stored_matches(e->codec, e->size, page) ||
+                    !shuffle_legal(e->codec, page, msg.shuf, client_seg) ||
+                    (client_addr + b.second) % 16 != 0) {
+                    err = INVALID_REQ;
+                    return false;
+                }
             } else if (tset) {
                 // The whole request against the entry's codec (geometry,
                 // aligned bases and offsets), once per codec; the page must
@@ -1266,6 +1291,7 @@ void Server::op_local_read(Conn* c, const LocalView& msg, const ReqCtx& ctx) {
                     it->second.perm = msg.perm;
                     it->second.xpose = msg.xpose;
                     it->second.cast = msg.cast;
+                    it->second.shuf = msg.shuf;
                     if (rotated) {
                         it->second.rot = msg.rot;
                         it->second.rot_table = msg.rot_table;

@@ -175,6 +175,11 @@ class Server {
         // permutation, a transpose or a cast.
         PageRotate rot;
         std::vector<float> rot_table;
+        // Shuffled pages (packed ops only): shuf.tokens != 0 says that the
+        // client holds every page as a shuffled cache block. Never together
+        // with a slice, a tensor set, a permutation, a transpose, a cast or a
+        // rotation.
+        PageShuffle shuf;
         const uint8_t* ipc = nullptr;
         size_t ipc_len = 0;
         std::vector<std::pair<std::string_view, uint64_t>> blocks;

@@ -253,6 +253,11 @@ bool Shard::submit_copy(CopyJob&& job) {
             !rotate_legal(job.codec, job.bytes_per_block, job.rot, seg))
             return false;
     }
+    // A shuffle is a client-side geometry of its own: next to none of the six.
+    const bool shuffled = shuffle_is_set(job.shuf);
+    if (shuffled && (sliced || tset || permuted || transposed || is_cast || rotated ||
+                     !shuffle_legal(job.codec, job.bytes_per_block, job.shuf, seg)))
+        return false;
     // A codec with a per-page scale needs one scale slot per block.
     const bool page_scale = page_codec_info(job.codec).page_scale;
     if (page_scale && (!job.scales || job.scales->size() < job.scales_off + n)) return false;
@@ -282,6 +287,7 @@ bool Shard::submit_copy(CopyJob&& job) {
             sub.cast = job.cast;
             sub.rot = job.rot;
             sub.rot_table = job.rot_table;
+            sub.shuf = job.shuf;
             sub.scales = job.scales;
             sub.scales_off = job.scales_off + off;
             sub.src.assign(job.src.begin() + static_cast<long>(off),
@@ -301,7 +307,7 @@ bool Shard::submit_copy(CopyJob&& job) {
     }
 
     if (!on_gpu()) {
-        if (transforms || rotated) return false;  // GPU-only
+        if (transforms || rotated || shuffled) return false;  // GPU-only
         // CPU shard: copies run inline on the caller (loop) thread.
         // A segmented page: the client side steps by the stride, the pool
         // side by the segment.
@@ -450,6 +456,8 @@ bool Shard::submit_copy(CopyJob&& job) {
     if (!aligned && is_cast) return false;
     // Nor the rotate kernels, for any codec.
     if (!aligned && rotated) return false;
+    // Nor the shuffle kernels, for any codec.
+    if (!aligned && shuffled) return false;
 
     // HIP stream enqueues are thread-safe; each job's ops precede its event
     // in stream order regardless of interleaving with other submitters, so
@@ -486,7 +494,7 @@ bool Shard::submit_copy(CopyJob&& job) {
     // (Segmented, sliced and tensor-set jobs always use the pinned-descriptor
     // kernels.)
     if (aligned && n <= 16 && !transforms && !segmented && !sliced && !tset && !permuted &&
-        !transposed && !is_cast && !rotated) {
+        !transposed && !is_cast && !rotated && !shuffled) {
         Slot* slot = acquire_slot(sc);
         if (!slot) return false;
         bool ok = gpu::set_device(opt_.device) &&
@@ -594,6 +602,21 @@ bool Shard::submit_copy(CopyJob&& job) {
                                opt_.device, sc.stream, job.codec, job.dir, dsrc, ddst,
                                slot->h_scale, static_cast<int>(take),
                                job.bytes_per_block / kPageElemBytes, aligned, seg, job.cast);
+            }
+        } else if (shuffled) {
+            if (!transforms) {
+                ok = ok && gpu::launch_copy_blocks_shuf(opt_.device, sc.stream, dsrc, ddst,
+                                                        static_cast<int>(take),
+                                                        job.bytes_per_block, aligned, seg,
+                                                        job.dir, job.shuf);
+            } else {
+                if (page_scale && job.dir == PageDir::kLoad)
+                    memcpy(slot->h_scale, job.scales->data() + job.scales_off + off,
+                           take * sizeof(float));
+                ok = ok && gpu::launch_transform_blocks_shuf(
+                               opt_.device, sc.stream, job.codec, job.dir, dsrc, ddst,
+                               slot->h_scale, static_cast<int>(take),
+                               job.bytes_per_block / kPageElemBytes, aligned, seg, job.shuf);
             }
         } else if (rotated) {
             // One launcher for every codec; fp8's scales ride in h_scale, and

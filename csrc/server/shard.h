@@ -104,6 +104,14 @@ class Shard {
         // 16-byte-aligned pointers and stride for every codec.
         PageRotate rot;
         std::vector<float> rot_table;
+        // Shuffled pages (core/page_codec.h, shuffle_legal): with
+        // shuf.tokens != 0 the CLIENT side holds every page as a shuffled
+        // cache block, and segments apply to that client page. Both
+        // directions, GPU shards only. Such a job never takes the
+        // inline-argument path and carries no slice, tensor set, permutation,
+        // transpose, cast or rotation; it needs 16-byte-aligned pointers and
+        // stride for every codec.
+        PageShuffle shuf;
         // Codecs with a per-page scale: block i's scale is
         // (*scales)[scales_off + i], written before done() by kStore and
         // read at submit by kLoad. Fan-out sub-jobs share the vector.

@@ -10,6 +10,7 @@ from .lib import (
     PageSlice,
     PagePermute,
     PageTranspose,
+    PageShuffle,
     PageCast,
     PageRotate,
     TensorSet,
@@ -41,6 +42,7 @@ __all__ = [
     "PageSlice",
     "PagePermute",
     "PageTranspose",
+    "PageShuffle",
     "PageCast",
     "PageRotate",
     "TensorSet",

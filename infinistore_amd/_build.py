@@ -30,6 +30,7 @@ SOURCES = [
     CSRC / "gpu" / "transpose.hip",
     CSRC / "gpu" / "cast.hip",
     CSRC / "gpu" / "rotate.hip",
+    CSRC / "gpu" / "shuffle.hip",
     CSRC / "fabric" / "verbs_fabric.cpp",
     CSRC / "server" / "shard.cpp",
     CSRC / "server" / "kv_index.cpp",
@@ -48,6 +49,7 @@ HIP_EXTRA_FLAGS = {
     "transpose.hip": _NO_PACKED_FP32,
     "cast.hip": _NO_PACKED_FP32,
     "rotate.hip": _NO_PACKED_FP32,
+    "shuffle.hip": _NO_PACKED_FP32,
 }
 
 HEADERS = sorted((CSRC).rglob("*.h")) + [Path(__file__)]

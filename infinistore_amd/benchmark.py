@@ -89,6 +89,16 @@ def parse_args():
                         "size")
     p.add_argument("--pa-head", type=int, default=128,
                    help="elements of one head of one token for --pa")
+    p.add_argument("--pa-shuffled", type=int, default=0, metavar="H",
+                   help="shuffled pages (local-GPU path): the buffers hold every page "
+                        "as a shuffled cache block, K [H, head/x, T, x] and V "
+                        "[H, T/x, head, x] with x = 16 / element size and head = "
+                        "--pa-head, and the store keeps it token-major; T follows from "
+                        "the page size")
+    p.add_argument("--pa-shuffled-baseline", action="store_true",
+                   help="with --pa-shuffled: what a reader does without shuffled pages, "
+                        "read whole token-major pages, then permute().contiguous() "
+                        "K and V of each buffer with torch (inside the timed read)")
     p.add_argument("--pa-baseline", action="store_true",
                    help="with --pa: what a reader does without transposed pages, "
                         "read whole token-major pages, then permute().contiguous() "
@@ -179,6 +189,16 @@ def rotate_k(buf, page_elems, rot, out=None):
     a, b = k[..., :P].float(), k[..., P:2 * P].float()
     o[..., :P] = (a * cs[:, 0] - b * cs[:, 1]).to(buf.dtype)
     o[..., P:2 * P] = (b * cs[:, 0] + a * cs[:, 1]).to(buf.dtype)
+
+
+def pa_shuffled_geometry(args, page_elems, es):
+    """lib.PageShuffle(T, H, head, element size) of --pa-shuffled, or None."""
+    if not args.pa_shuffled:
+        return None
+    per_token = 2 * args.pa_shuffled * args.pa_head
+    if args.pa_shuffled < 1 or args.pa_head < 1 or page_elems % per_token != 0:
+        raise SystemExit("--pa-shuffled needs a page of 2 x T x H x --pa-head elements")
+    return lib.PageShuffle(page_elems // per_token, args.pa_shuffled, args.pa_head, es)
 
 
 def slice_geometry(args):
@@ -387,6 +407,12 @@ def run_once(args, conn, local, device, bufs=None):
         pa_outs = [torch.zeros_like(d) for d in dsts]
         torch.cuda.synchronize()
 
+    # --pa-shuffled: every page is a shuffled cache block in the buffers.
+    shuf = pa_shuffled_geometry(args, page_elems, srcs[0].element_size()) if local else None
+    if shuf and args.pa_shuffled_baseline:  # allocated outside the timed window
+        pa_outs = [torch.zeros_like(d) for d in dsts]
+        torch.cuda.synchronize()
+
     # --fp8-cache: the buffers hold e4m3fn codes; the baseline moves bf16 pages
     # through staging tensors, allocated outside the timed windows.
     cast = lib.PageCast(FP8_CACHE_SCALES) if local and args.fp8_cache else None
@@ -411,6 +437,8 @@ def run_once(args, conn, local, device, bufs=None):
             g["page_permute"] = perm
         if xpose and permuted:
             g["page_transpose"] = xpose
+        if shuf and permuted:
+            g["page_shuffle"] = shuf
         return g
 
     # ---- write (layer-by-layer batches, like prefill; each step's slice
@@ -428,7 +456,7 @@ def run_once(args, conn, local, device, bufs=None):
             conn.write_pages(stages[t_idx].view(-1), [p[0] for p in pairs],
                              [p[1] for p in pairs], page_elems, quant=args.quant)
         elif local:
-            if args.quant or nseg > 1 or perm or xpose or cast:
+            if args.quant or nseg > 1 or perm or xpose or cast or shuf:
                 conn.write_pages(srcs[t_idx], [p[0] for p in pairs],
                                  [p[1] for p in pairs], page_elems,
                                  quant=args.quant, **geom(srcs[t_idx]))
@@ -470,7 +498,8 @@ def run_once(args, conn, local, device, bufs=None):
                 tickets.append(conn.read_pages_async(
                     stages[t_idx].view(-1) if stages else dsts[t_idx], ks, offs, page_elems,
                     **geom(dsts[t_idx],
-                           permuted=not (args.hnd_baseline or args.pa_baseline)), **rot_kw))
+                           permuted=not (args.hnd_baseline or args.pa_baseline
+                                         or args.pa_shuffled_baseline)), **rot_kw))
         for tk in tickets:
             conn.wait_read(tk)
         if rot and args.rotate_baseline:
@@ -503,6 +532,20 @@ def run_once(args, conn, local, device, bufs=None):
                 o5[:, 0].view(-1, H_, hd // x, T_, x).copy_(
                     d5[:, 0].reshape(-1, T_, H_, hd // x, x).permute(0, 2, 3, 1, 4))
                 o5[:, 1].view(-1, H_, hd, T_).copy_(d5[:, 1].permute(0, 2, 3, 1))
+            torch.cuda.synchronize()
+        if shuf and args.pa_shuffled_baseline:
+            # the second pass a reader needs today: token-major pages landed
+            # in the bounce buffers (dsts), the engine wants K as
+            # [H, head/x, T, x] and V as [H, T/x, head, x]
+            T_, H_, hd = shuf[:3]
+            x = 16 // shuf.elem_bytes
+            for d, o in zip(dsts, pa_outs):
+                d5 = d.view(-1, 2, T_, H_, hd)
+                o5 = o.view(-1, 2, H_ * hd * T_)
+                o5[:, 0].view(-1, H_, hd // x, T_, x).copy_(
+                    d5[:, 0].reshape(-1, T_, H_, hd // x, x).permute(0, 2, 3, 1, 4))
+                o5[:, 1].view(-1, H_, T_ // x, hd, x).copy_(
+                    d5[:, 1].reshape(-1, T_ // x, x, H_, hd).permute(0, 3, 1, 4, 2))
             torch.cuda.synchronize()
         if sg and args.slice_baseline:
             # the second pass a reader needs today: pick the heads out of the
@@ -738,6 +781,13 @@ def main():
                          "--fused-layers")
     if args.pa_baseline and not args.pa:
         raise SystemExit("--pa-baseline needs --pa")
+    if args.pa_shuffled_baseline and not args.pa_shuffled:
+        raise SystemExit("--pa-shuffled-baseline needs --pa-shuffled")
+    if args.pa_shuffled and (not args.local_gpu or args.segments != 1 or args.slice
+                             or args.fused_layers or args.hnd or args.pa or args.fp8_cache
+                             or args.rotate is not None):
+        raise SystemExit("--pa-shuffled needs --local-gpu and no --segments, --slice, "
+                         "--fused-layers, --hnd, --pa, --fp8-cache or --rotate")
     if args.pa and (not args.local_gpu or args.segments != 1 or args.slice
                     or args.fused_layers or args.hnd):
         raise SystemExit("--pa needs --local-gpu and no --segments, --slice, "

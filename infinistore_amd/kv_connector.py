@@ -90,7 +90,7 @@ class PagedKVConnector:
     def save_layer(self, layer: int, kv: torch.Tensor, page_keys: List[str],
                    page_offsets, page_elems: int, segments: int = 1,
                    segment_stride: int = 0, page_permute=None, page_transpose=None,
-                   page_cast=None):
+                   page_cast=None, page_shuffle=None):
         """Store this layer's pages of `kv` (offsets in elements). Call per
         layer as prefill produces them; uploads overlap later layers'
         compute (writes are async until sync()). segments / segment_stride:
@@ -100,8 +100,11 @@ class PagedKVConnector:
         page_transpose: `kv` holds each page as a paged-attention cache block
         (PageTranspose; local path only). page_cast: `kv` is an fp8 engine's
         cache, e4m3fn codes under a scale per half (PageCast; local path
-        only)."""
+        only). page_shuffle: `kv` holds each page as a shuffled cache block
+        (PageShuffle; local path only)."""
         keys = [self._key(layer, k) for k in page_keys]
+        if page_shuffle is not None and not self.local:
+            raise ValueError("shuffled pages use the local GPU path")
         if page_cast is not None and not self.local:
             raise ValueError("cast pages use the local GPU path")
         if self.local:
@@ -109,7 +112,8 @@ class PagedKVConnector:
                                   quant=self.quant, segments=segments,
                                   segment_stride=segment_stride,
                                   page_permute=page_permute,
-                                  page_transpose=page_transpose, page_cast=page_cast)
+                                  page_transpose=page_transpose, page_cast=page_cast,
+                                  page_shuffle=page_shuffle)
         elif page_permute is not None:
             raise ValueError("permuted pages use the local GPU path")
         elif page_transpose is not None:
@@ -129,11 +133,12 @@ class PagedKVConnector:
     def load_layer(self, layer: int, kv_out: torch.Tensor, page_keys: List[str],
                    page_offsets, page_elems: int, segments: int = 1,
                    segment_stride: int = 0, page_slice=None, page_permute=None,
-                   page_transpose=None, page_cast=None, page_rotate=None) -> bool:
+                   page_transpose=None, page_cast=None, page_rotate=None,
+                   page_shuffle=None) -> bool:
         """Gather this layer's cached pages into the engine's KV tensor.
         Returns False if any page is missing (caller falls back to compute).
         segments / segment_stride / page_slice / page_permute / page_transpose /
-        page_cast / page_rotate: as in
+        page_cast / page_rotate / page_shuffle: as in
         InfinityConnection.read_pages (page_elems is then the sliced page); a
         refused geometry raises ValueError."""
         keys = [self._key(layer, k) for k in page_keys]
@@ -145,6 +150,8 @@ class PagedKVConnector:
             raise ValueError("cast pages use the local GPU path")
         if page_rotate is not None and not self.local:
             raise ValueError("rotated reads use the local GPU path")
+        if page_shuffle is not None and not self.local:
+            raise ValueError("shuffled pages use the local GPU path")
         if segments != 1 and not self.local:
             raise ValueError("segmented pages use the local GPU path")
         if page_slice is not None and not self.local:
@@ -159,7 +166,7 @@ class PagedKVConnector:
                                      page_slice=page_slice,
                                      page_permute=page_permute,
                                      page_transpose=page_transpose, page_cast=page_cast,
-                                     page_rotate=page_rotate)
+                                     page_rotate=page_rotate, page_shuffle=page_shuffle)
             else:
                 self._ensure_mr(kv_out)
                 blocks = [(k, int(o)) for k, o in zip(keys, page_offsets)]
@@ -167,9 +174,10 @@ class PagedKVConnector:
             self.conn.sync()
             return True
         except ValueError:
-            if page_transpose is None and page_cast is None and page_rotate is None:
+            if (page_transpose is None and page_cast is None and page_rotate is None
+                    and page_shuffle is None):
                 return False
-            raise  # a transposed, cast or rotated read's arguments are checked by read_pages alone
+            raise  # such a read's arguments are checked by read_pages alone
         except Exception:
             return False
 
@@ -177,13 +185,14 @@ class PagedKVConnector:
                          page_keys: List[str], page_offsets, page_elems: int,
                          segments: int = 1, segment_stride: int = 0,
                          page_slice=None, page_permute=None, page_transpose=None,
-                         page_cast=None, page_rotate=None):
+                         page_cast=None, page_rotate=None, page_shuffle=None):
         """Ticketed prefetch (local path): push the gather and return a
         ticket; call wait_load(ticket) before touching kv_out. Lets decode
         overlap the next request's KV fetch with current compute. Returns
         None if any page was missing or the path is unavailable (caller
         falls back to load_layer / recompute). page_slice, page_permute,
-        page_transpose, page_cast and page_rotate as in load_layer."""
+        page_transpose, page_cast, page_rotate and page_shuffle as in
+        load_layer."""
         self.conn._permute_arg(page_permute, page_elems, segments, None, page_slice)
         if page_transpose is not None and not self.local:
             raise ValueError("transposed pages use the local GPU path")
@@ -191,6 +200,8 @@ class PagedKVConnector:
             raise ValueError("cast pages use the local GPU path")
         if page_rotate is not None and not self.local:
             raise ValueError("rotated reads use the local GPU path")
+        if page_shuffle is not None and not self.local:
+            raise ValueError("shuffled pages use the local GPU path")
         if not self.local:
             if segments != 1:
                 raise ValueError("segmented pages use the local GPU path")
@@ -208,9 +219,11 @@ class PagedKVConnector:
                                               page_permute=page_permute,
                                               page_transpose=page_transpose,
                                               page_cast=page_cast,
-                                              page_rotate=page_rotate)
+                                              page_rotate=page_rotate,
+                                              page_shuffle=page_shuffle)
         except ValueError:
-            if page_transpose is None and page_cast is None and page_rotate is None:
+            if (page_transpose is None and page_cast is None and page_rotate is None
+                    and page_shuffle is None):
                 return None
             raise  # as in load_layer
         except Exception:

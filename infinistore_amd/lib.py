@@ -305,6 +305,26 @@ class PageTranspose(NamedTuple):
     halves: int = 2
 
 
+class PageShuffle(NamedTuple):
+    """Client-side element order of a page (docs/design.md, "shuffled pages"):
+    the tensor holds each page as the shuffled cache block that assembly
+    paged-attention kernels read, per half and head one tile of tokens x
+    head_dim elements, with X = 16 // elem_bytes, as [head_dim // X, tokens, X]
+    (form "k") or [tokens // X, head_dim, X] (form "v"), while the store keeps,
+    and every other reader sees, [halves, tokens, heads, head_dim]. forms[o] is
+    half o's form; a one-half page (separate key and value tensors) uses
+    forms[0]. elem_bytes must be the tensor's element size. A bf16 engine's
+    key_cache [blocks, H, hd/8, T, 8] and value_cache [blocks, H, T/8, hd, 8] in
+    one [2, blocks, ...] allocation: PageShuffle(T, H, hd) with segments=2."""
+
+    tokens: int
+    heads: int
+    head_dim: int
+    elem_bytes: int = 2
+    halves: int = 2
+    forms: tuple = ("k", "v")
+
+
 class PageCast:
     """Client-side element type of a page (docs/design.md, "cast pages"): the
     tensor (torch.float8_e4m3fn or uint8) holds each page as one-byte OCP
@@ -648,6 +668,81 @@ class InfinityConnection:
                              "segment stride")
         return geo
 
+    SHUFFLE_FORMS = {"k": 1, "v": 2}
+
+    def _shuffle_arg(self, page_shuffle, cache, offsets, page_size: int, segments: int,
+                     segment_stride: int, quant=None, page_slice=None, tensor_set=None,
+                     page_permute=None, page_transpose=None, page_cast=None, page_rotate=None):
+        """Refuse (ValueError) a shuffled request the store cannot serve,
+        before anything is sent; the geometry rule is the native
+        shuffle_legal. Returns what the native calls take: (halves, tokens,
+        heads, head_dim, element bytes, form_k, form_v)."""
+        if (page_slice is not None or tensor_set is not None or page_permute is not None
+                or page_transpose is not None or page_cast is not None
+                or page_rotate is not None):
+            raise ValueError("page_shuffle cannot be combined with page_slice, tensor_set, "
+                             "page_permute, page_transpose, page_cast or page_rotate")
+        if not self.local_connected:
+            raise ValueError("shuffled pages use the local GPU path")
+        sh = PageShuffle(*page_shuffle)
+        forms = tuple(sh.forms) if isinstance(sh.forms, (tuple, list)) else ()
+        if not 1 <= len(forms) <= 2 or any(f not in self.SHUFFLE_FORMS for f in forms):
+            raise ValueError('PageShuffle forms are one or two of "k" and "v"')
+        fk, fv = self.SHUFFLE_FORMS[forms[0]], self.SHUFFLE_FORMS[forms[-1]]
+        es = cache.element_size()
+        if sh.elem_bytes != es:
+            raise ValueError(f"PageShuffle elem_bytes is {sh.elem_bytes}, the cache's element "
+                             f"size is {es}")
+        if quant is not None and quant not in self.QUANT_MODES:
+            raise ValueError(f"unsupported quant mode {quant!r}")
+        if quant is not None and cache.dtype != torch.bfloat16:
+            raise ValueError(f"{quant} quant requires a bf16 cache")
+        geo = (sh.halves, sh.tokens, sh.heads, sh.head_dim, es, fk, fv)
+        if (min(geo) < 1 or max(geo) >= 1 << 32 or not 0 < page_size < 1 << 60
+                or not 0 < segments < 1 << 32 or segment_stride < 0):
+            raise ValueError("PageShuffle values, page_size and segments must be positive")
+        if not _native._dbg_shuffle_legal(self.QUANT_CODECS[quant], page_size * es, geo,
+                                          segments, segment_stride * es):
+            raise ValueError(
+                "illegal page shuffle: page_size is halves * tokens * heads * head_dim with "
+                "halves 1 or 2; tokens and head_dim are multiples of 16 // elem_bytes "
+                "(head_dim of 32 with mxfp4); a quant needs 2-byte elements; halves * heads is "
+                f"a multiple of segments, at most {self.MAX_PAGE_SEGMENTS}, with a "
+                "segment_stride of at least one segment")
+        offs = np.asarray(offsets, dtype=np.uint64)
+        if (cache.data_ptr() % 16 != 0 or (offs * np.uint64(es) % np.uint64(16)).any()
+                or (segments != 1 and segment_stride * es % 16 != 0)):
+            raise ValueError("shuffled pages need a 16-byte-aligned cache, page offsets and "
+                             "segment stride")
+        if len(offs) and (int(offs.max()) + (segments - 1) * segment_stride
+                          + page_size // segments > cache.numel()):
+            raise ValueError("a shuffled page extends outside the tensor")
+        return geo
+
+    def _rw_shuffled(self, op, cache, keys, offsets, page_size, segments, segment_stride, shuf,
+                     sync=False, flags=0, ticketed=False):
+        """One shuffled request. Returns the ticket (0 unless ticketed)."""
+        offs = np.asarray(offsets, dtype=np.uint64)
+        es = cache.element_size()
+        args = (es, page_size * es, cache.data_ptr(), _remap_device_id(cache))
+        ticket = 0
+        if ticketed:
+            if not isinstance(keys, (bytes, bytearray, memoryview)):
+                keys = self.pack_keys(keys)
+            ret, ticket = self.conn.rw_local_blob_async(
+                op, keys, offs, *args, segments, segment_stride, None, None, None, None, None,
+                shuf)
+        elif isinstance(keys, (bytes, bytearray, memoryview)):
+            ret = self.conn.rw_local_blob(op, keys, offs, *args, sync, flags, segments,
+                                          segment_stride, None, None, None, None, None, shuf)
+        else:
+            ret = self.conn.rw_local_keys(op, keys, offs, *args, sync, flags, segments,
+                                          segment_stride, None, None, None, None, None, shuf)
+        if ret < 0:
+            what = "write to" if op == self.OP_W else "read from"
+            raise Exception(f"Failed to {what} infinistore, ret = {ret}")
+        return ticket
+
     CAST_DTYPES = (torch.float8_e4m3fn, torch.uint8)
 
     def _cast_arg(self, page_cast, cache, offsets, page_size: int, segments: int,
@@ -874,7 +969,8 @@ class InfinityConnection:
                     segments: Optional[int] = None, segment_stride: int = 0,
                     tensor_set=None, page_permute: Optional[PagePermute] = None,
                     page_transpose: Optional[PageTranspose] = None,
-                    page_cast: Optional[PageCast] = None, **unsupported):
+                    page_cast: Optional[PageCast] = None,
+                    page_shuffle: Optional[PageShuffle] = None, **unsupported):
         """sync=True completes the write in ONE round trip (the response is
         sent when the copy finishes); sync=False (default) returns after the
         server accepts, so uploads overlap compute — call sync() later.
@@ -943,13 +1039,35 @@ class InfinityConnection:
         and offsets must be 16-byte aligned; anything the server would refuse
         is a ValueError before anything is sent.
 
+        page_shuffle=PageShuffle(tokens, heads, head_dim): `cache` holds each
+        page as a shuffled cache block (see PageShuffle) and the stored page
+        is the token-major [halves, tokens, heads, head_dim] one,
+        byte-identical to what a token-major writer stores. Works with every
+        quant and with segments; local path only, with none of the other page_*
+        arguments or tensor_set; cache, offsets and stride must be 16-byte
+        aligned; an illegal geometry is a ValueError before anything is sent.
+
         Slices are read-only: write_pages has no page_slice parameter, and
         passing one is a ValueError."""
+        if page_shuffle is not None and "page_rotate" in unsupported:
+            raise ValueError("page_shuffle cannot be combined with page_slice, tensor_set, "
+                             "page_permute, page_transpose, page_cast or page_rotate")
         if "page_slice" in unsupported:
             raise ValueError("page_slice is read-only: there is no sliced write")
         if unsupported:
             raise TypeError(f"write_pages() got an unexpected keyword argument "
                             f"{next(iter(unsupported))!r}")
+        if page_shuffle is not None:
+            segments = 1 if segments is None else segments
+            if tensor_set is None:
+                self._verify(cache)
+            shuf = self._shuffle_arg(page_shuffle, cache, offsets, page_size, segments,
+                                     segment_stride, quant, None,
+                                     tensor_set, page_permute, page_transpose, page_cast)
+            self._rw_shuffled(self.OP_W, cache, keys, offsets, page_size, segments,
+                              segment_stride, shuf, sync,
+                              self.QUANT_MODES[quant][0] if quant else 0)
+            return 0
         if tensor_set is not None:
             if page_permute is not None:
                 raise ValueError("page_permute cannot be combined with page_slice or "
@@ -1033,7 +1151,8 @@ class InfinityConnection:
                    page_permute: Optional[PagePermute] = None,
                    page_transpose: Optional[PageTranspose] = None,
                    page_cast: Optional[PageCast] = None,
-                   page_rotate: Optional[PageRotate] = None):
+                   page_rotate: Optional[PageRotate] = None,
+                   page_shuffle: Optional[PageShuffle] = None):
         """segments / segment_stride: scatter each page into that many equal
         pieces of `cache` (see write_pages), however the page was written.
         Local path only.
@@ -1077,7 +1196,21 @@ class InfinityConnection:
         caches); local path only, bf16 only, 16-byte-aligned cache and
         offsets; not together with page_slice, tensor_set, page_permute,
         page_transpose or page_cast; anything the server would refuse is a
-        ValueError before anything is sent."""
+        ValueError before anything is sent.
+
+        page_shuffle: deliver each page as a shuffled cache block (see
+        write_pages), however it was written. page_size must be the written
+        one. With none of the other page_* arguments or tensor_set."""
+        if page_shuffle is not None:
+            segments = 1 if segments is None else segments
+            if tensor_set is None:
+                self._verify(cache)
+            shuf = self._shuffle_arg(page_shuffle, cache, offsets, page_size, segments,
+                                     segment_stride, None, page_slice, tensor_set, page_permute,
+                                     page_transpose, page_cast, page_rotate)
+            self._rw_shuffled(self.OP_R, cache, keys, offsets, page_size, segments,
+                              segment_stride, shuf)
+            return
         if page_rotate is not None:
             segments = 1 if segments is None else segments
             if tensor_set is None:
@@ -1163,14 +1296,25 @@ class InfinityConnection:
                          page_permute: Optional[PagePermute] = None,
                          page_transpose: Optional[PageTranspose] = None,
                          page_cast: Optional[PageCast] = None,
-                         page_rotate: Optional[PageRotate] = None):
+                         page_rotate: Optional[PageRotate] = None,
+                         page_shuffle: Optional[PageShuffle] = None):
         """Ticketed read (local path, shm ring): pushes the request and
         returns a ticket; call wait_read(ticket) before using the data. Lets
         an engine overlap its own work (or further requests) with the copy —
         e.g. prefetching the next sequence's KV pages while decoding. Falls
         back to a blocking read (ticket 0) when the ring is unavailable.
         segments / segment_stride / page_slice / tensor_set / page_permute /
-        page_transpose / page_cast / page_rotate as in read_pages."""
+        page_transpose / page_cast / page_rotate / page_shuffle as in
+        read_pages."""
+        if page_shuffle is not None:
+            segments = 1 if segments is None else segments
+            if tensor_set is None:
+                self._verify(cache)
+            shuf = self._shuffle_arg(page_shuffle, cache, offsets, page_size, segments,
+                                     segment_stride, None, page_slice, tensor_set, page_permute,
+                                     page_transpose, page_cast, page_rotate)
+            return self._rw_shuffled(self.OP_R, cache, keys, offsets, page_size, segments,
+                                     segment_stride, shuf, ticketed=True)
         if page_rotate is not None:
             segments = 1 if segments is None else segments
             if tensor_set is None:

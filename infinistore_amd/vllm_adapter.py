@@ -44,7 +44,7 @@ from typing import Dict, List, Optional, Sequence
 import torch
 
 from .kv_connector import PagedKVConnector, token_page_hashes
-from .lib import PageCast, PagePermute, PageSlice, PageTranspose
+from .lib import PageCast, PagePermute, PageShuffle, PageSlice, PageTranspose
 
 
 class InfiniStoreKVAdapter:
@@ -109,7 +109,12 @@ class InfiniStoreKVAdapter:
             ``n_kv = cache_kv_heads``. Every page then travels as a transposed
             page (docs/design.md, "transposed pages"); ``kv_layout="kv_major"``
             is vLLM's one ``[2, num_blocks, ...]`` allocation. The same keys,
-            quants and restrictions as for "hnd".
+            quants and restrictions as for "hnd". "pa_shuffled": the
+            shuffled block that assembly paged-attention kernels read, per
+            head K as ``[head/x, block_tokens, x]`` and V as
+            ``[block_tokens/x, head, x]``, ``x = 16 // element_size``. Every
+            page then travels as a shuffled page (docs/design.md, "shuffled
+            pages"); the same keys, quants and restrictions as for "pa".
         cache_dtype, k_scale, v_scale: "auto" (default): the cache tensors
             hold what the store treats as the page. "fp8_e4m3": vLLM's
             ``kv_cache_dtype="fp8"`` cache, one-byte e4m3fn codes
@@ -125,7 +130,7 @@ class InfiniStoreKVAdapter:
     """
 
     KV_LAYOUTS = ("block_major", "kv_major")
-    CACHE_LAYOUTS = ("nhd", "hnd", "pa")
+    CACHE_LAYOUTS = ("nhd", "hnd", "pa", "pa_shuffled")
     LAYER_PAGES = ("per_layer", "fused")
     CACHE_DTYPES = ("auto", "fp8_e4m3")
 
@@ -160,6 +165,7 @@ class InfiniStoreKVAdapter:
             raise ValueError(f"cache_layout must be one of {self.CACHE_LAYOUTS}")
         self._page_permute = None
         self._pa = None
+        self._pa_shuffled = None
         if cache_layout == "hnd":
             if cache_kv_heads is None or cache_kv_heads < 1:
                 raise ValueError('cache_layout="hnd" needs cache_kv_heads')
@@ -190,6 +196,22 @@ class InfiniStoreKVAdapter:
             # (tokens, heads, head_dim); inner_k follows the tensor at each call
             self._pa = (block_tokens, cache_kv_heads,
                         page_elems // (2 * block_tokens * cache_kv_heads))
+        elif cache_layout == "pa_shuffled":
+            if cache_kv_heads is None or cache_kv_heads < 1:
+                raise ValueError('cache_layout="pa_shuffled" needs cache_kv_heads')
+            if not local:
+                raise ValueError('cache_layout="pa_shuffled" uses shuffled pages, which need '
+                                 "the local GPU path")
+            if head_range is not None or layer_pages == "fused":
+                raise ValueError('cache_layout="pa_shuffled" cannot be combined with head_range '
+                                 'or layer_pages="fused": a shuffled page takes neither a '
+                                 "slice nor a tensor set")
+            if block_tokens < 1 or page_elems % (2 * block_tokens * cache_kv_heads) != 0:
+                raise ValueError('with cache_layout="pa_shuffled" page_elems is '
+                                 "2*block_tokens*cache_kv_heads*head_dim")
+            # (tokens, heads, head_dim); the element size follows the tensor at each call
+            self._pa_shuffled = (block_tokens, cache_kv_heads,
+                                 page_elems // (2 * block_tokens * cache_kv_heads))
         elif cache_kv_heads is not None:
             raise ValueError('cache_kv_heads goes with cache_layout="hnd"')
         if layer_pages == "fused":
@@ -395,6 +417,8 @@ class InfiniStoreKVAdapter:
             geo["page_permute"] = self._page_permute
         if self._pa is not None:
             geo["page_transpose"] = PageTranspose(*self._pa, 16 // kv_cache.element_size())
+        if self._pa_shuffled is not None:
+            geo["page_shuffle"] = PageShuffle(*self._pa_shuffled, kv_cache.element_size())
         if self._page_cast is not None:
             geo["page_cast"] = self._page_cast
         if self.kv_layout == "kv_major":

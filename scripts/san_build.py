@@ -96,7 +96,7 @@ def main():
                 return 1
             print(f"  [{mode}] {s}")
         objs.append(o)
-    for hip in ("gpu", "quant_error", "transpose", "cast", "rotate"):
+    for hip in ("gpu", "quant_error", "transpose", "cast", "rotate", "shuffle"):
         gpu_o = f"{build}/{hip}.o"
         gpu_src = os.path.join(REPO, f"csrc/gpu/{hip}.hip")
         if not os.path.exists(gpu_o) or os.path.getmtime(gpu_o) < os.path.getmtime(gpu_src):
